@@ -2,7 +2,7 @@
 """bench.py -- throughput of the batched sea-ice column update on MI355X (BASELINE.json metric:
 column-timesteps/sec, achieved HBM GB/s vs peak).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One bench "step" = ONE launch of the hot path that advances every column `--substeps` model time steps (a launch is
 one pass of the time-loop body over the whole resident ensemble, repeated substeps times inside the kernel; columns
@@ -17,11 +17,16 @@ Multi-GPU: columns are sharded by rank, no data-path collective exists (weak sca
 torchrun the ranks come from RANK / LOCAL_RANK / WORLD_SIZE; a bare `python bench.py --gpus N` (N > 1) starts N fresh
 rank processes itself, before this process has made any GPU call.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the JSON line.  The line carries
   roofline      algorithmic bytes per launch / mean launch duration (HIP events on the launch stream)
+and, with --full only (each leg takes runs of its own after the timed steps):
   cpu_baseline  the CPU oracle (C port of the reference algorithm) timed on this host: all cores and one core
   extra         (N = 1) the same geometry started from other stages of the SHEBA year: open water, growth, the melt
                 season (flushing, flooding, regridding: the unfused paths), and the first-300-days rate they imply
+
+--dump-outputs DIR writes the state the timed steps left behind (what samsim_get_state returns) on a fixed, seeded sample of
+column windows of rank 0, one float64 DIR/<name>.npy per layer array ([nlayer, columns]) and per scalar ([columns]), plus
+n_active and status, so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import hashlib
@@ -339,6 +344,38 @@ def timed_window(g, substeps, launches, warmup, barrier):
     return wall, kernel_ms, float(work_after - work_before), nfail
 
 
+DUMP_SEED = 20240601
+DUMP_BYTES = 48 << 20       # the whole dump stays below 64 MB
+DUMP_MAX_COLUMNS = 4096
+
+
+def dump_outputs(g, out_dir):
+    """the state the timed steps left, on a fixed, seeded sample of 64-column windows (same columns for the same --ncol).  Left out
+    because no step boundary defines them: S_br and ray (step-internal hand-over arrays, tests/helpers.py), the diagnostics the HIP
+    path only evaluates at output points (DEAD_BETWEEN_OUTPUTS) and the layers below N_active (written as 0)"""
+    from samsim_amd.capi import A, ARRAYS, S, SCALARS
+    from tests.helpers import DEAD_BETWEEN_OUTPUTS
+    lay_names = [n for n in ARRAYS if n not in ("S_br", "ray")]
+    scal_names = [n for n in SCALARS if n not in DEAD_BETWEEN_OUTPUTS]
+    per_column = 8 * (len(lay_names) * g.nlayer + len(scal_names) + 2)
+    w = min(64, g.ncol)
+    nwin = max(1, min(g.ncol // w, min(DUMP_MAX_COLUMNS, DUMP_BYTES // per_column) // w))
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(g.ncol // w, nwin, replace=False)) * w
+    parts = [g.get_state(int(c0), w) for c0 in starts]
+    cols = np.concatenate([np.arange(c0, c0 + w) for c0 in starts])
+    lay = np.concatenate([p.lay for p in parts], axis=2)
+    scal = np.concatenate([p.scal for p in parts], axis=1)
+    n_active = np.concatenate([p.n_active for p in parts])
+    lay[:, np.arange(g.nlayer)[:, None] >= n_active[None, :]] = 0.0
+    out = {n: lay[A[n]] for n in lay_names}
+    out.update({n: scal[S[n]] for n in scal_names})
+    out["n_active"] = n_active.astype(np.float64)
+    out["status"] = g.get_status()[0][cols].astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def stage_windows(g, cfg, args, forcing):
     """the same geometry started from other stages of the SHEBA year (fixtures made by tests/golden/make_stage_fixtures.py)"""
     from samsim_amd import testcases as tcs
@@ -388,6 +425,11 @@ def main():
                          "(testcase 4 as shipped)")
     ap.add_argument("--sites", type=int, default=1,
                     help="forcing sets (samsim_set_forcing_sites): the tables replicated N times, column c on set c mod N")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (seeded sample of columns, float64) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own after the timed steps: the stage windows (extra) and the CPU "
+                         "baseline (cpu_baseline); --no-extra / --no-cpu-baseline drop one of them")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--ref-steps", type=int, default=1500000,
                     help="cpu_baseline: steps of testcase 4 from open water on which the reference binary and the port are timed "
@@ -402,6 +444,8 @@ def main():
                     help="comma-separated HIP device per local rank (default: device = local rank); '0,0' rehearses two ranks "
                          "on a one-GPU box")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
@@ -471,6 +515,8 @@ def main():
             dist.barrier()
 
     wall, kernel_ms, cells, nfail = timed_window(g, args.substeps, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(g, args.dump_outputs)
 
     # who ran where: every rank reports the device its handle lives on (ordinal and PCI bus id, from the library), its column range
     # and its own rate; rank 0 prints them and refuses a record in which two ranks shared a GPU unless that was asked for
@@ -518,7 +564,7 @@ def main():
                          "algorithmic_bytes_per_launch": bytes_per_colstep * ncol * args.substeps,
                          "lib_md5": lib_md5()},
         }
-        if world == 1 and not args.no_extra and args.workload == "sheba" and args.sites == 1:
+        if args.full and world == 1 and not args.no_extra and args.workload == "sheba" and args.sites == 1:
             ex = stage_windows(g, cfg, args, forcing)
             rates = {k: v["column_timesteps_per_s"] for k, v in ex.items()}
             rates["day200"] = value
@@ -527,7 +573,7 @@ def main():
                             "first_300_days": {"column_timesteps_per_s": first_300_days(rates),
                                                "how": "time-weighted over the stage windows day 0 / 75 / 150 / 200 (headline) / 250 / 300; "
                                                       "each stage stands for the days around it"}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, st, pert, clock, forcing, col0, args.cpu_seconds, args.ref_steps)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -9,7 +9,7 @@ V=samsim_amd/csrc/variants
 md5sum samsim_amd/csrc/libsamsim_hip.so $V/*.so | tee $O/md5.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 # 1. the default bench line (stage windows, cpu baseline with the reference binary)
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err || (tail -5 $O/bench_default.err; exit 1)
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || (tail -5 $O/bench_default.err; exit 1)
 python - <<'PY'
 import json; d=json.load(open("gpurun_out/r3x/bench_default.json")); print("default %.4e"%d["value"], d["ms_per_step"], round(d["roofline"]["frac"],4), d["failed_columns"]); print(json.dumps(d["cpu_baseline"])[:1800]); print({k:("%.3e"%v["column_timesteps_per_s"], v["failed_columns"]) for k,v in d["extra"]["stages"].items()})
 PY
@@ -49,7 +49,7 @@ grep -h verdict $O/path_equiv_*.json
 tools/div_probe | tee $O/div_probe.txt
 tools/layout_probe 8 24 | tee $O/layout_probe.txt
 SAMSIM_HIP_LIB=$V/libsamsim_hip_st2.so timeout -k 10 200 python tools/stamps.py --fixture sheba_ensemble_80_day345.npz --launches 2 > $O/counters_melt345.json
-timeout -k 10 300 python bench.py --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err
 python - <<'PY'
 import json; d=json.load(open("gpurun_out/r3x/bench_steps20.json")); print("steps20 %.4e"%d["value"], d["ms_per_step"], round(d["roofline"]["frac"],4), d["failed_columns"], d["roofline"].get("traffic"))
 PY
