@@ -168,6 +168,9 @@ int samsim_set_ocean(samsim_handle *h, const double *dfl_q_bottom_col, const dou
 /* initial state of init(testcase) (mo_init.f90:141-1978) or a checkpoint; col0 and s->ncol select a window.
  * The two perturbation slots SAMSIM_S_DT2M / SAMSIM_S_PRECIP_SCALE are owned by samsim_set_forcing: set_state
  * ignores them, get_state returns them. */
+/* Both move the layer arrays of the window through a device staging buffer in pieces of at most SAMSIM_STAGE_MAX_BYTES: the
+ * buffer never holds more, whatever the window. */
+#define SAMSIM_STAGE_MAX_BYTES (256ull << 20)
 int samsim_set_state(samsim_handle *h, const samsim_state_soa *s, int64_t col0);
 int samsim_get_state(samsim_handle *h, samsim_state_soa *s, int64_t col0);
 int samsim_set_clock(samsim_handle *h, const samsim_clock *c);

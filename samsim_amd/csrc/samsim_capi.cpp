@@ -59,8 +59,8 @@ struct samsim_handle {
   double *spec = nullptr;      // hand-over block of the up sweep, [DEV_NSPEC][ncol]
   int32_t *flags = nullptr;    // COLF_* per column
   void *d_stat = nullptr;      // block partials of samsim_get_ensemble_stats
-  double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand and kept:
-  size_t stage_n = 0;          // no hipMalloc / hipFree -- both wait for the whole device -- per call
+  double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
+  size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
   double *bgc = nullptr, *bgc_bot = nullptr, *bfl = nullptr, *out_bgc = nullptr, *out_bgc_bot = nullptr;
   int32_t n_bgc = 0;
@@ -87,6 +87,26 @@ struct samsim_handle {
 };
 
 namespace {
+
+// Upper bound of the staging buffer (SAMSIM_STAGE_MAX_BYTES, 256 MiB): samsim_set_state / samsim_get_state move a window through
+// it in pieces of at most this many bytes, so the buffer never holds more, whatever the window.  Unbounded, one full-handle
+// get_state at SAMSIM_MAX_NCOL x 80 layers would need 136 GB of staging beside the 151 GB handle.  256 MiB is 0.2 % of such a
+// handle, yet a piece is still ~10 ms of copying over the host link against some tens of microseconds of fixed cost (one scatter /
+// gather launch and one synchronisation), so pieces cost no throughput.  It also bounds the scatter / gather grid (32 Mi threads
+// per launch; a whole window of 15 arrays of 80 layers would pass the 2^32 work-items of one dispatch from 3.6 M columns on).
+constexpr size_t kStageBytes = (size_t)SAMSIM_STAGE_MAX_BYTES;
+
+// columns of one staging piece for narr arrays of N layers: a multiple of 64 (whole column blocks) within kStageBytes
+static_assert(kStageBytes / ((size_t)SAMSIM_NARR * SAMSIM_MAX_NLAYER * sizeof(double)) >= 64, "a staging piece holds a column block");
+size_t stage_cols(int narr, size_t N) { return (kStageBytes / ((size_t)narr * N * sizeof(double))) & ~(size_t)63; }
+
+// rows x cols doubles between two row-major blocks of row lengths dpitch / spitch (in doubles): one plain copy when both are
+// contiguous (a window that fits one piece), else one 2D copy
+hipError_t copy_rows(double *dst, size_t dpitch, const double *src, size_t spitch, size_t cols, size_t rows, hipMemcpyKind kind,
+                     hipStream_t s) {
+  if (dpitch == cols && spitch == cols) return hipMemcpyAsync(dst, src, rows * cols * sizeof(double), kind, s);
+  return hipMemcpy2DAsync(dst, dpitch * sizeof(double), src, spitch * sizeof(double), cols * sizeof(double), rows, kind, s);
+}
 
 // the handle's staging buffer with room for n doubles
 hipError_t stage_for(samsim_handle *h, size_t n) {
@@ -506,12 +526,15 @@ int samsim_set_state(samsim_handle *h, const samsim_state_soa *s, int64_t col0) 
   const size_t N = (size_t)s->nlayer, nc = (size_t)h->ncol, w = (size_t)s->ncol;
   for (size_t i = 0; i < w; ++i) if (s->n_active[i] < 1 || s->n_active[i] > (int)N) return SAMSIM_ERR_ARG;
   HIPCHK(hipStreamSynchronize(h->stream));
-  {
-    const size_t n = (size_t)s->narr * N * w;
-    HIPCHK(stage_for(h, n));
-    HIPCHK(hipMemcpyAsync(h->stage, s->lay, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  // the window in pieces of at most stage_cols columns: rows [narr][N] of the piece's columns are gathered from the caller's
+  // [narr][N][w] into the staging buffer by one 2D copy, then scattered into the device layout
+  const size_t pc = stage_cols(s->narr, N), rows = (size_t)s->narr * N;
+  HIPCHK(stage_for(h, rows * (w < pc ? w : pc)));
+  for (size_t p0 = 0; p0 < w; p0 += pc) {
+    const size_t pw = w - p0 < pc ? w - p0 : pc, n = rows * pw;
+    HIPCHK(copy_rows(h->stage, pw, s->lay + p0, w, pw, rows, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(lay_window<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->lay, h->stage, (int)s->narr, (int)N, nc,
-                       (size_t)col0, w);
+                       (size_t)col0 + p0, pw);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
   }
@@ -540,13 +563,14 @@ int samsim_get_state(samsim_handle *h, samsim_state_soa *s, int64_t col0) {
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  {
-    const size_t n = (size_t)s->narr * N * w;
-    HIPCHK(stage_for(h, n));
+  const size_t pc = stage_cols(s->narr, N), rows = (size_t)s->narr * N;   // pieces as in samsim_set_state
+  HIPCHK(stage_for(h, rows * (w < pc ? w : pc)));
+  for (size_t p0 = 0; p0 < w; p0 += pc) {
+    const size_t pw = w - p0 < pc ? w - p0 : pc, n = rows * pw;
     hipLaunchKernelGGL(lay_window<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->lay, h->stage, (int)s->narr, (int)N, nc,
-                       (size_t)col0, w);
+                       (size_t)col0 + p0, pw);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->lay, h->stage, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(copy_rows(s->lay + p0, w, h->stage, pw, pw, rows, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   HIPCHK(hipMemcpy2D(s->scal, w * sizeof(double), h->scal + col0, nc * sizeof(double), w * sizeof(double), (size_t)SAMSIM_NSCAL,
