@@ -1940,44 +1940,52 @@ __device__ __forceinline__ void sweep_down_fused(Col &c, const Ctx &x, bool stor
     store_psi = store_default || decide_psi;   // (a deciding sweep over fewer than three layers has nothing left to skip)
   }
   c.psi_full = store_psi;
-  // The interior layers 3 <= j < N_active, two per trip: the two request buffers swap roles from one layer to the next, so with
-  // both layers in one loop body no buffer is copied into the other (and the hand-over of layer j to C(j) of the next layer is a
-  // renaming): the single-layer loop spent 35 of its 265 vector instructions on those copies.  A stretch with an odd number of
-  // layers ends with one single-layer step that does copy its buffer (at most three per sweep).
+  // The interior layers 3 <= j < N_active, three per trip.  Three rows are alive at any layer -- the layer's own (`raw`, which
+  // finish() forms in the registers of the buffer it was requested into), the next one and the one being requested -- so the
+  // roles go round the three buffers once in three layers: with three layers in one loop body no buffer is copied into another
+  // and the hand-over of layer j to C(j) of the next layer is a renaming.  (One layer per trip spent 35 of its 265 vector
+  // instructions on those copies; two per trip still ended every trip by copying the row it had requested one layer before into
+  // the registers the next trip expects it in, behind `s_waitcnt vmcnt(3..0)`: a full drain, the second layer's own stores
+  // included, every other layer.)  A column whose interior layers end inside a trip, and the 0-2 layers a stretch has left
+  // over, take single-layer steps that do copy their buffer (at most two per column and six per wave and sweep).
   {
     const int b0 = g.n_top, b1 = g.n_top + g.n_middle;
+    Ld ahead3 = ahead;
+    auto single = [&](const int j, const double th_s, const double rth_s) {
+      ahead2 = load_ld(j + 2 <= N ? j + 2 : N);
+      layer(j, ahead, th_s, rth_s, std::false_type{}, std::false_type{});
+      raw = finish(ahead, j + 1);
+      ahead = ahead2;
+    };
     int j = 3;
     for (int stretch = 0; stretch < 3; ++stretch) {
       const int hi_s = stretch == 0 ? b0 : (stretch == 1 ? b1 : N);
       const int hi = hi_s < jmax - 1 ? hi_s : jmax - 1;           // last interior layer of the stretch in the longest column of the wave
       const double th_s = stretch == 1 ? LAYU(SAMSIM_A_THICK, g.n_top + 1) : g.thick_0, rth_s = recip(th_s);
-      for (; j + 1 <= hi; j += 2) {
+      for (; j + 2 <= hi; j += 3) {
         ISA_MARK("D_ITER_BEGIN");
         ST_MARK(ST_DFUSED);
-        if (j + 1 < Na) {                                  // both layers are interior layers of this column: one straight-line body
-          ST_COUNT(CT_DOWN_TRIPS, 2);
+        if (j + 2 < Na) {                                  // all three are interior layers of this column: one straight-line body
+          ST_COUNT(CT_DOWN_TRIPS, 3);
           ahead2 = load_ld(j + 2 <= N ? j + 2 : N);        // layer j+2 -> second buffer
           layer(j, ahead, th_s, rth_s, std::false_type{}, std::false_type{});
           raw = finish(ahead, j + 1);
-          ahead = load_ld(j + 3 <= N ? j + 3 : N);         // layer j+3 -> first buffer
+          ahead3 = load_ld(j + 3 <= N ? j + 3 : N);        // layer j+3 -> third buffer
           layer(j + 1, ahead2, th_s, rth_s, std::false_type{}, std::false_type{});
           raw = finish(ahead2, j + 2);
-        } else if (j < Na) {                               // layer j is the column's last interior layer
+          ahead = load_ld(j + 4 <= N ? j + 4 : N);         // layer j+4 -> first buffer
+          layer(j + 2, ahead3, th_s, rth_s, std::false_type{}, std::false_type{});
+          raw = finish(ahead3, j + 3);
+        } else if (j < Na) {                               // the column's interior layers end with layer j or j+1
+          ISA_MARK("D_RARE_BEGIN");
           ST_COUNT(CT_DOWN_TRIPS, 1);
-          ahead2 = load_ld(j + 2 <= N ? j + 2 : N);
-          layer(j, ahead, th_s, rth_s, std::false_type{}, std::false_type{});
-          raw = finish(ahead, j + 1);
+          single(j, th_s, rth_s);
+          if (j + 1 < Na) { ST_COUNT(CT_DOWN_TRIPS, 1); single(j + 1, th_s, rth_s); }
         }
         ISA_MARK("D_ITER_END");
       }
-      if (j <= hi) {                                       // odd number of layers in this stretch
-        if (j < Na) {
-          ahead2 = load_ld(j + 2 <= N ? j + 2 : N);
-          layer(j, ahead, th_s, rth_s, std::false_type{}, std::false_type{});
-          raw = finish(ahead, j + 1);
-          ahead = ahead2;
-        }
-        ++j;
+      for (; j <= hi; ++j) {                               // the layers the stretch has left over
+        if (j < Na) single(j, th_s, rth_s);
       }
     }
   }
@@ -2176,10 +2184,10 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
   // a wave the same for one column as for 64) -- it then only runs the second getT chain, and says so for all its columns
   // (COLF_DIRTY: the full first sweep gives a column the same bits as the fused one).  A wave that does not flush after all has lost
   // nothing but the fused first sweep of one step.
-  auto body = [&](const int k, const double th_k, const double rth_k, auto top_tag, auto lite_tag) {
+  auto body = [&](const int k, const UL &row, const double th_k, const double rth_k, auto top_tag, auto lite_tag) {
     constexpr bool TOP = decltype(top_tag)::value;
     constexpr bool LITE = decltype(lite_tag)::value;
-    const double H_k = cur.H, m_k = cur.m, S_k = cur.S;
+    const double H_k = row.H, m_k = row.m, S_k = row.S;
     double H_abs = H_k;
     const double m = m_k;
     if (TOP) {
@@ -2246,30 +2254,50 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
   auto load4 = [&](int j) -> UL { UL u = load3(j); u.th = LAYU(SAMSIM_A_THICK, j); return u; };
   auto layers = [&](auto lite_tag) {
   if (regular_wave) {
-    cur = load3(Na); nxt = load3(Na >= 2 ? Na - 1 : 1); nn = nxt;   // layers k, k-1, k-2
-
+    // Three layers per trip.  The three request buffers take the roles "this layer", "the next", "the one being requested" in
+    // turn; with three textual copies of the layer in one trip the roles rotate by NAME and no buffer is ever copied into another.
+    // (One layer per trip rotated them with `cur = nxt; nxt = nn;`, and those copies -- of rows requested at the top of the same
+    // trip -- each waited for its row: the request lead was one layer body, with the wait at the end of it.)  The rows are the
+    // wave's, not the lane's: every lane requests row k-2 at layer k whether or not the layer exists in its column (k > Na: it
+    // only sits the layer out), so a shorter column finds its bottom layer in `a` when the wave arrives there, in whichever copy
+    // that is.  The 0-2 layers a stretch has left over run one per trip and do copy their buffers (at most six per sweep).
+    const int kc = kmax >= 2 ? kmax - 1 : 1;
+    UL a = load3(kmax), b = load3(kc), d = b;       // layers k, k-1, k-2
+    auto one = [&](const int k, const UL &row, UL &req, const double th_s, const double rth_s) {
+      req = load3(k >= 3 ? k - 2 : 1);
+      if (k <= Na) body(k, row, th_s, rth_s, std::false_type{}, lite_tag);
+    };
     const int b0 = g.n_top, b1 = g.n_top + g.n_middle;
     int k = kmax;
     for (int stretch = 0; stretch < 3; ++stretch) {
       const int klo = stretch == 0 ? b1 + 1 : (stretch == 1 ? b0 + 1 : 2);
       // (formed where the stretch begins -- the elastic block's thickness is one load per sweep -- so that only this pair is carried)
       const double th_s = stretch == 1 ? LAYU(SAMSIM_A_THICK, g.n_top + 1) : g.thick_0, rth_s = recip(th_s);
-      for (; k >= klo; --k) {
+      for (; k - 2 >= klo; k -= 3) {
         ISA_MARK("U_ITER_BEGIN");
         ST_MARK(ST_UP);
-        if (k > Na) continue;
-        nn = load3(k >= 3 ? k - 2 : 1);    // (three layers ahead: no faster, gpurun_out/r3f)
-        body(k, th_s, rth_s, std::false_type{}, lite_tag);
-        cur = nxt; nxt = nn;
+        one(k, a, d, th_s, rth_s);
+        ISA_MARK("U_LAYER_2");
+        one(k - 1, b, a, th_s, rth_s);
+        ISA_MARK("U_LAYER_3");
+        one(k - 2, d, b, th_s, rth_s);
         ISA_MARK("U_ITER_END");
       }
+      for (; k >= klo; --k) {
+        ISA_MARK("U_REST_BEGIN");
+        ST_MARK(ST_UP);
+        one(k, a, d, th_s, rth_s);
+        a = b; b = d;
+        ISA_MARK("U_REST_END");
+      }
     }
+    cur = a;
   } else {
     cur = load4(Na); nxt = load4(Na >= 2 ? Na - 1 : 1); nn = nxt;
     for (int k = kmax; k >= 2; --k) {
       if (k > Na) continue;
       nn = load4(k >= 3 ? k - 2 : 1);
-      body(k, cur.th, recip(cur.th), std::false_type{}, lite_tag);
+      body(k, cur, cur.th, recip(cur.th), std::false_type{}, lite_tag);
       cur = nxt; nxt = nn;
     }
   }
@@ -2278,7 +2306,7 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
   if (lite) { ST_COUNT(CT_LITE, 1); layers(std::true_type{}); } else layers(std::false_type{});
   __builtin_amdgcn_wave_barrier();   // the row flags are complete: the next readers are the down sweeps of the next step
   if (neg_salt || lite) c.flags |= COLF_DIRTY;
-  body(1, LAYU(SAMSIM_A_THICK, 1), 0.0, std::true_type{}, std::false_type{});
+  body(1, cur, LAYU(SAMSIM_A_THICK, 1), 0.0, std::true_type{}, std::false_type{});
   if (!alive) return;
   // hand-over block for prologue_top_layer of the next step
   if (!lite) {
