@@ -57,6 +57,16 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: mean, min, max, std
   END TYPE
 
+  ! samsim_get_profile_stats (ABI 6): enum samsim_profile_axis / samsim_profile_origin and the request
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_PROFILE_BY_LAYER = 0, SAMSIM_PROFILE_BY_DEPTH = 1, &
+                                   SAMSIM_PROFILE_FROM_TOP = 0, SAMSIM_PROFILE_FROM_BOTTOM = 1
+  INTEGER, PARAMETER :: SAMSIM_PROFILE_MAX_BINS = 1024, SAMSIM_PROFILE_MAX_ARRAYS = 8
+  TYPE, BIND(C) :: samsim_profile_request
+     INTEGER(c_int32_t) :: struct_size, axis, origin, nbins, narrays
+     INTEGER(c_int32_t) :: arrays(SAMSIM_PROFILE_MAX_ARRAYS)     ! enum samsim_layer_array values (0-based)
+     REAL(c_double)     :: z0, dz                                ! depth axis only, metres
+  END TYPE samsim_profile_request
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -179,6 +189,28 @@ MODULE mo_samsim_capi
        INTEGER(c_int32_t), VALUE :: nslots
        INTEGER(c_int32_t), INTENT(in) :: slots(*)        ! enum samsim_scalar values (0-based), -1 = N_active
        TYPE(samsim_stat), INTENT(out) :: out(*)
+     END FUNCTION
+     !> statistics of the layer profiles per layer or per depth bin; out(nbins, narrays), bin fastest (ABI 6)
+     INTEGER(c_int) FUNCTION samsim_get_profile_stats(h, rq, out) BIND(C, name='samsim_get_profile_stats')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(samsim_profile_request), INTENT(in) :: rq
+       TYPE(samsim_stat), INTENT(out) :: out(*)
+     END FUNCTION
+     !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
+     INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), INTENT(out) :: device
+       CHARACTER(kind=c_char), INTENT(out) :: pci_bus_id(*)
+       INTEGER(c_int32_t), VALUE :: len
+     END FUNCTION
+     !> from how many 64-column blocks a step runs as two concurrent launches (0 = never) and the first part's share (ABI 5)
+     INTEGER(c_int) FUNCTION samsim_set_launch_split(h, min_blocks, first_part_eighths) BIND(C, name='samsim_set_launch_split')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: min_blocks
+       INTEGER(c_int32_t), VALUE :: first_part_eighths
      END FUNCTION
      INTEGER(c_int) FUNCTION samsim_get_work(h, cells, colsteps) BIND(C, name='samsim_get_work')
        IMPORT

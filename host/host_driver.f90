@@ -4,7 +4,8 @@
 !! runs on the GPU behind the C-ABI of include/samsim.h for `ncol` columns at once.
 !!
 !! New surface the reference does not have (SURVEY.md, introduction): a namelist file `samsim.nml`
-!!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites /
+!!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites,
+!!                 profile_bins, profile_dz, profile_origin /
 !! (col0 / ncol_total: this process owns the global columns col0 .. col0+ncol-1 of an ensemble of ncol_total -- one host
 !! process per GPU, contiguous column ranges, no exchange between them, SURVEY.md section 8e)
 !!   &samsim_flags <any flag of mo_data.f90:136-155 or scalar set by mo_init> /       (overrides init(testcase))
@@ -31,6 +32,9 @@ MODULE mo_data
   INTEGER(c_int64_t)  :: max_steps = -1
   CHARACTER(len=256)  :: sites(16) = ' '      !< directories with flux_sw/flux_lw/T2m/precip.txt.input; column c reads sites(MOD(c-1,n)+1)
   CHARACTER(len=1024) :: restart_in = ' ', restart_out = ' '   !< binary checkpoint files (samsim_amd/checkpoint.py format)
+  INTEGER             :: profile_bins = 0    !< > 0: ensemble statistics of T, S_bu and psi_l in profile_bins depth bins at every output point
+  REAL(wp)            :: profile_dz = 0._wp  !< width of a depth bin [m]
+  INTEGER             :: profile_origin = 0  !< 0 depth below the ice surface, 1 height above the ice bottom
   INTEGER             :: i_time, i_time_out
   REAL(wp)            :: fl_q_bottom = 0._wp, T_top = 0._wp, fl_sw = 0._wp, fl_rest = 0._wp, T2m = 0._wp, tank_depth = 0._wp
   INTEGER             :: N_bgc = 1
@@ -478,8 +482,46 @@ CONTAINS
     WRITE(51, '(F14.1,I10,24ES16.8)') time, q(1)%count, (q(j)%mean, q(j)%min, q(j)%max, q(j)%std, j = 1, 6)
   END SUBROUTINE output_ensemble
 
+  !> dat_ens_profile_{T,S_bu,psi_l}.dat: opened only when the run asks for profile statistics (profile_bins > 0)
+  SUBROUTINE output_begin_profile()
+    INTEGER :: recl
+    IF (profile_bins <= 0) RETURN
+    recl = 64 + 74*profile_bins
+    OPEN(52, file='./output/dat_ens_profile_T.dat',     STATUS='replace', Recl=recl)
+    OPEN(53, file='./output/dat_ens_profile_S_bu.dat',  STATUS='replace', Recl=recl)
+    OPEN(54, file='./output/dat_ens_profile_psi_l.dat', STATUS='replace', Recl=recl)
+  END SUBROUTINE output_begin_profile
+
+  !> One row per output point and file: the time, then for every depth bin count, mean, min, max and standard deviation of the
+  !! array over the ensemble (samsim_get_profile_stats: the profiles as step functions of depth, averaged over each bin).
+  SUBROUTINE output_profile(h, time)
+    TYPE(c_ptr), INTENT(in) :: h
+    REAL(wp),    INTENT(in) :: time
+    TYPE(samsim_profile_request) :: rq
+    TYPE(samsim_stat), ALLOCATABLE :: q(:, :)
+    CHARACTER(len=64) :: fmt
+    INTEGER :: a, b
+    IF (profile_bins <= 0) RETURN
+    rq%struct_size = INT(c_sizeof(rq), c_int32_t)
+    rq%axis = SAMSIM_PROFILE_BY_DEPTH; rq%origin = INT(profile_origin, c_int32_t)
+    rq%nbins = INT(profile_bins, c_int32_t); rq%narrays = 3
+    rq%arrays = 0
+    rq%arrays(1:3) = (/ A_T - 1, A_S_BU - 1, A_PSI_L - 1 /)
+    rq%z0 = 0._wp; rq%dz = profile_dz
+    ALLOCATE(q(profile_bins, 3))
+    CALL samsim_check(samsim_get_profile_stats(h, rq, q), 'samsim_get_profile_stats')
+    WRITE(fmt, '(A,I0,A)') '(F14.1,', profile_bins, '(I10,4ES16.8))'
+    DO a = 1, 3
+       WRITE(51 + a, fmt) time, (q(b, a)%count, q(b, a)%mean, q(b, a)%min, q(b, a)%max, q(b, a)%std, b = 1, profile_bins)
+    END DO
+    DEALLOCATE(q)
+  END SUBROUTINE output_profile
+
   SUBROUTINE output_end()
     INTEGER :: u
+    IF (profile_bins > 0) THEN
+       CLOSE(52); CLOSE(53); CLOSE(54)
+    END IF
     DO u = 30, 35
        CLOSE(u)
     END DO
@@ -622,15 +664,26 @@ CONTAINS
     INTEGER(c_int32_t), ALLOCATABLE, TARGET :: ona(:), status(:), err_layer(:), site_of_column(:)
     INTEGER(c_int64_t), ALLOCATABLE :: err_step(:)
     INTEGER(c_int64_t) :: n, done, total, cells, colsteps
-    INTEGER :: nfail, count0, count1, rate
+    INTEGER :: nfail, count0, count1, rate, j
+    INTEGER(c_int32_t) :: dev_ordinal
+    CHARACTER(kind=c_char) :: pci(32)
     REAL(wp) :: time, thick1
 
     CALL init(testcase, nml_unit)
     CALL output_begin(cfg%nlayer)
     IF (cfg%bgc_flag == 2) CALL output_begin_bgc(cfg%nlayer)
+    CALL output_begin_profile()
     CALL output_settings(description, testcase)
 
     CALL samsim_check(samsim_create(cfg, ncol, INT(device, c_int32_t), h), 'samsim_create')
+    ! which GPU this process (one rank per GPU) really runs on
+    pci = c_null_char
+    CALL samsim_check(samsim_get_device(h, dev_ordinal, pci, 32_c_int32_t), 'samsim_get_device')
+    j = 1
+    DO WHILE (j < 32 .AND. pci(j) /= c_null_char)
+       j = j + 1
+    END DO
+    WRITE(*, '(A,I0,A,I0,A,I0,A,32A1)') ' columns ', col0, ' .. ', col0 + ncol - 1, ' on HIP device ', dev_ordinal, ', PCI ', pci(1:j-1)
     IF (cfg%atmoflux_flag == 2) THEN
        CALL sub_input()
        ALLOCATE(site_of_column(ncol))
@@ -682,6 +735,7 @@ CONTAINS
              CALL output_bgc(cfg%nlayer, ona(1), obgc(1, :, :), obot(1, :), olay(1, :, :))
           END IF
           CALL output_ensemble(h, o%time)
+          CALL output_profile(h, o%time)
           time = o%time
           thick1 = olay(1, 1, A_THICK)
           ! console progress line, mo_grotz.f90:371-381
@@ -728,7 +782,7 @@ PROGRAM SAMSIM
   CHARACTER*12000 :: description
   LOGICAL         :: have_nml
   NAMELIST /samsim_run/ testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, &
-       restart_out, sites
+       restart_out, sites, profile_bins, profile_dz, profile_origin
 
   testcase    = 1
   description = 'MI355X-native batched column solver'

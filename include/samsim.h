@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SAMSIM_ABI_VERSION 5
+#define SAMSIM_ABI_VERSION 6
 #define SAMSIM_MAX_NLAYER 1024
 
 /* -------- configuration: every flag of mo_data.f90:136-155 plus the scalars mo_init sets -------- */
@@ -236,6 +236,47 @@ typedef struct samsim_stat {
   double  mean, min, max, std;
 } samsim_stat;
 int samsim_get_ensemble_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, samsim_stat *out);
+
+/* Ensemble statistics of the layer profiles, by layer and by depth (ABI 6): the same five numbers as above for the layer arrays --
+ * the reference's main products dat_T, dat_S_bu, dat_psi_l, dat_thick ..., which its plot scripts read as step functions of
+ * depth -- per bin, reduced on the device; only per-bin results come back.  out[narrays][nbins].  A request is served in passes
+ * of one array and at most 64 bins; a pass walks the layers of every column once and reads only the rows it needs (the array --
+ * S_abs and m for S_bu --, and thick on the depth axis, which is therefore read once per array and chunk, twice from the bottom), so
+ * the cost grows with narrays * ceil(nbins / 64).
+ *
+ *   Columns.  Only columns with status == 0 count.  Na = n_active[c].
+ *   Layer value.  a_k is the stored value of the array in layer k, 1 <= k <= Na; for SAMSIM_A_S_BU it is S_abs(k)/m(k) where
+ *     m(k) != 0 (the stored value elsewhere): what samsim_get_state returns.  After any launch every row is current (the last
+ *     step of a launch stores everything), so the statistics describe the state samsim_get_state would return now.
+ *   Depth coordinate.  Z_0 = 0, Z_k = Z_{k-1} + thick(k) by sequential double additions, k ascending; H = Z_Na.  Snow is not
+ *     part of the coordinate; the lowest active layer counts with its full thick.
+ *   SAMSIM_PROFILE_BY_LAYER.  Bin b (0-based) receives, FROM_TOP, a_{b+1} of the columns with b+1 <= Na; FROM_BOTTOM, a_{Na-b}
+ *     of the columns with Na-b >= 1.
+ *   SAMSIM_PROFILE_BY_DEPTH.  Edges e_b = z0 + b*dz (the product is rounded, then the sum; no fused multiply-add).  Layer k
+ *     covers [lo_k, hi_k): FROM_TOP [Z_{k-1}, Z_k), FROM_BOTTOM [H - Z_k, H - Z_{k-1}).  o_kb = max(0, min(hi_k, e_{b+1}) -
+ *     max(lo_k, e_b)); L_b = sum_k o_kb and W_b = sum_k o_kb*a_k, both over ascending k.  A column contributes to bin b if and
+ *     only if L_b > 0, with the value v = W_b / L_b (IEEE division): the step-function profile averaged over the bin.
+ *   Statistics.  Per (array, bin) over the contributing columns: count, mean, min, max and the population standard deviation
+ *     sqrt(sum (v-mean)^2 / count) (formed from deviations, never from sum v^2 - n mean^2); with count == 0 the other four are 0.0.
+ *     Fixed grid, fixed order of combination, no floating-point atomics: two calls on the same state return the same bytes.
+ *   Errors, all found before any device work.  SAMSIM_ERR_ABI: wrong struct_size.  SAMSIM_ERR_ARG: axis, origin, nbins (also
+ *     > nlayer with BY_LAYER), narrays or an array id out of range; with BY_DEPTH a non-finite z0 or dz, z0 < 0 or dz <= 0.
+ *   Like every getter the call waits for the handle's streams; it changes neither the state, the clock nor the output snapshot.
+ *   Device scratch: at most SAMSIM_PROFILE_SCRATCH_BYTES whatever ncol and the request are (every pass reuses it); allocated on first use, kept in the handle, freed by samsim_destroy. */
+#define SAMSIM_PROFILE_MAX_BINS   1024   /* = SAMSIM_MAX_NLAYER */
+#define SAMSIM_PROFILE_MAX_ARRAYS 8
+#define SAMSIM_PROFILE_SCRATCH_BYTES (3ull << 20)
+enum samsim_profile_axis   { SAMSIM_PROFILE_BY_LAYER = 0, SAMSIM_PROFILE_BY_DEPTH = 1 };
+enum samsim_profile_origin { SAMSIM_PROFILE_FROM_TOP = 0, SAMSIM_PROFILE_FROM_BOTTOM = 1 };
+typedef struct samsim_profile_request {
+  int32_t struct_size;   /* = sizeof(samsim_profile_request) */
+  int32_t axis, origin;
+  int32_t nbins;         /* 1..SAMSIM_PROFILE_MAX_BINS; BY_LAYER: also <= nlayer */
+  int32_t narrays;       /* 1..SAMSIM_PROFILE_MAX_ARRAYS */
+  int32_t arrays[SAMSIM_PROFILE_MAX_ARRAYS];   /* enum samsim_layer_array */
+  double  z0, dz;        /* BY_DEPTH only: z0 >= 0, dz > 0, finite; metres */
+} samsim_profile_request;
+int samsim_get_profile_stats(samsim_handle *h, const samsim_profile_request *rq, samsim_stat *out);
 
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);

@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _CFG_INT_FIELDS = [
     "struct_size", "testcase", "nlayer", "n_top", "n_middle", "n_bottom",
@@ -51,6 +51,21 @@ class Clock(C.Structure):
 class Stat(C.Structure):
     """samsim_stat"""
     _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("min", C.c_double), ("max", C.c_double), ("std", C.c_double)]
+
+
+PROFILE_MAX_BINS = 1024
+PROFILE_MAX_ARRAYS = 8
+PROFILE_AXES = {"layer": 0, "depth": 1}
+PROFILE_ORIGINS = {"top": 0, "bottom": 1}
+
+
+class ProfileRequest(C.Structure):
+    """samsim_profile_request"""
+    _fields_ = [("struct_size", C.c_int32), ("axis", C.c_int32), ("origin", C.c_int32), ("nbins", C.c_int32),
+                ("narrays", C.c_int32), ("arrays", C.c_int32 * PROFILE_MAX_ARRAYS), ("z0", C.c_double), ("dz", C.c_double)]
+
+
+STAT_DTYPE = np.dtype([("count", np.int64), ("mean", np.float64), ("min", np.float64), ("max", np.float64), ("std", np.float64)])
 
 
 class OutputSoA(C.Structure):
@@ -218,6 +233,8 @@ class Solver:
         f.argtypes, f.restype = [vp, C.POINTER(C.c_int32), C.c_char_p, C.c_int32], C.c_int
         f = self._f("set_launch_split")
         f.argtypes, f.restype = [vp, i64, C.c_int32], C.c_int
+        f = self._f("get_profile_stats")
+        f.argtypes, f.restype = [vp, C.POINTER(ProfileRequest), C.c_void_p], C.c_int
 
     # -- API
     def set_forcing(self, fl_sw, fl_lw, T2m, precip, dT2m=None, precip_scale=None):
@@ -376,6 +393,33 @@ class Solver:
         slots = (C.c_int32 * len(names))(*[-1 if n == "N_active" else S[n] for n in names])
         out = (Stat * len(names))()
         self._chk(self._f("get_ensemble_stats")(self._h, len(names), slots, out), "get_ensemble_stats")
+        return {n: out[i] for i, n in enumerate(names)}
+
+    def profile_stats_raw(self, rq: ProfileRequest) -> np.ndarray:
+        """samsim_get_profile_stats with the request as given (no checks on this side): structured array [narrays][nbins]"""
+        out = np.zeros((max(0, min(rq.narrays, PROFILE_MAX_ARRAYS)), max(0, min(rq.nbins, PROFILE_MAX_BINS))), dtype=STAT_DTYPE)
+        buf = np.zeros(max(1, out.size), dtype=STAT_DTYPE)
+        self._chk(self._f("get_profile_stats")(self._h, C.byref(rq), buf.ctypes.data), "get_profile_stats")
+        out.ravel()[:] = buf[:out.size]
+        return out
+
+    def profile_stats(self, names, axis="layer", origin="top", nbins=None, z0=0.0, dz=None):
+        """{name: structured array [nbins] with fields count, mean, min, max, std} over the columns without a STOP code
+        (samsim_get_profile_stats): names from ARRAYS; axis "layer" (bin b = layer b+1 from the top, or N_active-b from the
+        bottom; nbins defaults to nlayer) or "depth" (bins [z0 + b dz, z0 + (b+1) dz) in metres below the ice surface or above
+        the ice bottom; nbins and dz are required)"""
+        names = list(names)
+        if axis == "depth" and (nbins is None or dz is None):
+            raise ValueError("axis='depth' needs nbins and dz")
+        rq = ProfileRequest()
+        rq.struct_size = C.sizeof(ProfileRequest)
+        rq.axis, rq.origin = PROFILE_AXES[axis], PROFILE_ORIGINS[origin]
+        rq.nbins = self.nlayer if nbins is None else int(nbins)
+        rq.narrays = len(names)
+        for i, n in enumerate(names[:PROFILE_MAX_ARRAYS]):
+            rq.arrays[i] = A[n]
+        rq.z0, rq.dz = float(z0), float(0.0 if dz is None else dz)
+        out = self.profile_stats_raw(rq)
         return {n: out[i] for i, n in enumerate(names)}
 
     def run_to_output(self) -> Output:

@@ -17,6 +17,10 @@
 #include "samsim_device.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
+// samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS)
+extern "C" hipError_t samsim_launch_profile(const double *lay, const int32_t *n_active, const int32_t *status, long long ncol, int N,
+                                            int axis, int origin, int array, int b0, int nb, int nbins, double z0, double dz,
+                                            ProfPartial *part, samsim_stat *out, hipStream_t stream);
 
 namespace {
 
@@ -59,6 +63,7 @@ struct samsim_handle {
   double *spec = nullptr;      // hand-over block of the up sweep, [DEV_NSPEC][ncol]
   int32_t *flags = nullptr;    // COLF_* per column
   void *d_stat = nullptr;      // block partials of samsim_get_ensemble_stats
+  void *d_prof = nullptr;      // samsim_get_profile_stats: the waves' partials of one pass, then the results (kProfScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -185,6 +190,12 @@ __global__ void __launch_bounds__(kStatBlock) stat_kernel(const double *__restri
     else { part[blockIdx.x].sum = s_sum[0]; part[blockIdx.x].mn = s_mn[0]; part[blockIdx.x].mx = s_mx[0]; part[blockIdx.x].n = s_n[0]; }
   }
 }
+
+// device scratch of samsim_get_profile_stats: the partials of one pass (every pass reuses them), then the results of the largest request
+constexpr size_t kProfPartBytes = sizeof(ProfPartial) * DEV_PROF_GRID * DEV_PROF_BINS;
+constexpr size_t kProfScratch = kProfPartBytes + sizeof(samsim_stat) * SAMSIM_PROFILE_MAX_ARRAYS * SAMSIM_PROFILE_MAX_BINS;
+static_assert(kProfScratch <= SAMSIM_PROFILE_SCRATCH_BYTES && SAMSIM_PROFILE_SCRATCH_BYTES <= (64ull << 20), "profile scratch bound of samsim.h");
+static_assert(SAMSIM_PROFILE_MAX_BINS == SAMSIM_MAX_NLAYER, "a layer-axis request may ask for every layer");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -428,7 +439,7 @@ void samsim_destroy(samsim_handle *h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   (void)hipFree(h->lay); (void)hipFree(h->scal); (void)hipFree(h->n_active); (void)hipFree(h->status);
   (void)hipFree(h->err_layer); (void)hipFree(h->err_step); (void)hipFree(h->work);
-  (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->stage);
+  (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
   (void)hipFree(h->ocean_dflq); (void)hipFree(h->ocean_sbu);
@@ -846,6 +857,36 @@ int samsim_get_ensemble_stats(samsim_handle *h, int32_t nslots, const int32_t *s
     }
     out[i] = st;
   }
+  return SAMSIM_OK;
+}
+
+int samsim_get_profile_stats(samsim_handle *h, const samsim_profile_request *rq, samsim_stat *out) {
+  // every check of the request first: nothing below touches the device before the request is known to be good
+  if (!h || !rq || !out) return SAMSIM_ERR_ARG;
+  if (rq->struct_size != (int32_t)sizeof(samsim_profile_request)) return SAMSIM_ERR_ABI;
+  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
+  if (!depth && rq->axis != SAMSIM_PROFILE_BY_LAYER) return SAMSIM_ERR_ARG;
+  if (rq->origin != SAMSIM_PROFILE_FROM_TOP && rq->origin != SAMSIM_PROFILE_FROM_BOTTOM) return SAMSIM_ERR_ARG;
+  if (rq->nbins < 1 || rq->nbins > SAMSIM_PROFILE_MAX_BINS || (!depth && rq->nbins > h->cfg.nlayer)) return SAMSIM_ERR_ARG;
+  if (rq->narrays < 1 || rq->narrays > SAMSIM_PROFILE_MAX_ARRAYS) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < rq->narrays; ++i)
+    if (rq->arrays[i] < 0 || rq->arrays[i] >= SAMSIM_NARR) return SAMSIM_ERR_ARG;
+  if (depth && (!std::isfinite(rq->z0) || !std::isfinite(rq->dz) || rq->z0 < 0.0 || !(rq->dz > 0.0))) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  if (!h->d_prof) HIPCHK(hipMalloc(&h->d_prof, kProfScratch));
+  ProfPartial *d_part = (ProfPartial *)h->d_prof;
+  samsim_stat *d_out = (samsim_stat *)((char *)h->d_prof + kProfPartBytes);
+  // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
+  // the next pass writes them
+  for (int i = 0; i < rq->narrays; ++i)
+    for (int b0 = 0; b0 < rq->nbins; b0 += DEV_PROF_BINS) {
+      const int nb = rq->nbins - b0 < DEV_PROF_BINS ? rq->nbins - b0 : DEV_PROF_BINS;
+      HIPCHK(samsim_launch_profile(h->lay, h->n_active, h->status, h->ncol, h->cfg.nlayer, rq->axis, rq->origin, rq->arrays[i], b0, nb,
+                                   rq->nbins, depth ? rq->z0 : 0.0, depth ? rq->dz : 1.0, d_part, d_out + (size_t)i * rq->nbins + b0, h->stream));
+    }
+  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_stat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }
 
