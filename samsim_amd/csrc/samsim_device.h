@@ -1,7 +1,7 @@
 // samsim_device.h -- device-side data layout shared by the kernels and the C-ABI host code.
 //
 // HBM layout (one allocation per handle, sized for ncol columns of nlayer layers):
-//   lay  [ncol/64][nlayer][DEV_NARR][64] float64   layer arrays per 64-column block (SAMSIM_BLOCKED below): a wave's 64
+//   lay  [ncol/64][nlayer][DEV_NARR][64] float64   layer arrays per 64-column block (see DEV_ROWB below): a wave's 64
 //                                           lanes read 512 contiguous bytes for every (array, layer) pair, the sixteen arrays of
 //                                           a layer row are 8 KiB, a wave's whole block is one contiguous piece
 //   scal [SAMSIM_NSCAL][ncol]     float64   per-column scalars
@@ -14,22 +14,20 @@
 
 // device-internal layer arrays: the public ones (enum samsim_layer_array) followed by scratch
 enum dev_layer_array {
-  D_V_EX = SAMSIM_NARR,   // scratch row: equivalent resistance R(k) of flush3 (mo_flush.f90:137-145), after the up sweep;
-                          // before it, D_HR = the half resistance thick/(2k) the down sweep hands to the up sweep
-  D_HR = D_V_EX,
+  D_V_EX = SAMSIM_NARR,   // scratch row: equivalent resistance R(k) of flush3 (mo_flush.f90:137-145), written by its up pass and read
+                          // by its down pass; nothing else uses the row
   DEV_NARR
 };
 
-// SAMSIM_BLOCKED 1 (default): the layer block is stored per 64-column block -- [block][layer][array][64 lanes] -- so that a wave's
-// column block is one contiguous piece (DEV_NARR * 512 B per layer): every array of a layer row sits within the immediate offset
-// range of one row address, a row address is scalar arithmetic, and the lane's offset is the same register for the whole launch.
-// 0 = [array][layer][column].  The boundary (samsim_set_state / samsim_get_state) keeps [array][layer][column] either way.
-#define DEV_NARR_C 16                                  // = DEV_NARR
-static_assert(DEV_NARR == DEV_NARR_C, "DEV_NARR_C");
-#define DEV_ROWB ((size_t)DEV_NARR_C * 512)            // bytes of one layer of one 64-column block
+// The layer block is stored per 64-column block -- [block][layer][array][64 lanes] -- so that a wave's column block is one
+// contiguous piece (DEV_NARR * 512 B per layer): every array of a layer row sits within the immediate offset range of one row
+// address, a row address is scalar arithmetic, and the lane's offset is the same register for the whole launch.
+// The boundary (samsim_set_state / samsim_get_state) keeps [array][layer][column].
+static_assert(DEV_NARR == 16, "the kernel's LAY() reaches the arrays of a layer row with immediate offsets a*512 - 4096: sixteen arrays");
+#define DEV_ROWB ((size_t)DEV_NARR * 512)              // bytes of one layer of one 64-column block
 // doubles in the layer block of a handle, and the position of element (array a, 0-based layer k0, column col)
-#define DEV_LAY_DOUBLES(N, ncol) ((((size_t)(ncol) + 63) / 64) * (size_t)(N) * DEV_NARR_C * 64)
-#define DEV_LAY_INDEX(a, k0, col, N, ncol) ((((size_t)(col) >> 6) * (size_t)(N) + (size_t)(k0)) * (DEV_NARR_C * 64) + (size_t)(a) * 64 + ((size_t)(col) & 63))
+#define DEV_LAY_DOUBLES(N, ncol) ((((size_t)(ncol) + 63) / 64) * (size_t)(N) * DEV_NARR * 64)
+#define DEV_LAY_INDEX(a, k0, col, N, ncol) ((((size_t)(col) >> 6) * (size_t)(N) + (size_t)(k0)) * (DEV_NARR * 64) + (size_t)(a) * 64 + ((size_t)(col) & 63))
 
 // per-column values handed from the up sweep of step n to the top-layer prologue of step n+1: [DEV_NSPEC][ncol]
 enum dev_spec {

@@ -98,3 +98,22 @@ def test_product_does_not_reference_the_oracle():
             if f.endswith((".py", ".cpp", ".hip", ".h", "Makefile")):
                 txt = open(os.path.join(dp, f), errors="ignore").read()
                 assert "liboracle" not in txt and "samsim_oracle" not in txt and "oracle_lib" not in txt, f
+
+
+def test_every_header_of_the_library_is_a_prerequisite_of_it():
+    """build() goes through make, so a header the Makefile does not know would leave a stale library behind, silently: right after
+    a build make has nothing to do (-q: exit 0), and touching any header of samsim_amd/csrc or include/samsim.h (-W: as if it
+    were new) makes the library out of date (exit 1)"""
+    import glob
+    import shutil
+    import subprocess
+    csrc = os.path.join(ROOT, "samsim_amd", "csrc")
+    if shutil.which("make") is None or not os.path.exists(os.path.join(csrc, "libsamsim_hip.so")):
+        pytest.skip("needs make and the built library")
+    query = ["make", "-C", csrc, "-q"]
+    assert subprocess.call(query + ["libsamsim_hip.so"]) == 0, "the library is out of date right after the build"
+    # (-W takes a file by the name make knows it under: relative to samsim_amd/csrc)
+    headers = sorted(os.path.basename(h) for h in glob.glob(os.path.join(csrc, "*.h"))) + ["../../include/samsim.h"]
+    assert len(headers) >= 13 and os.path.exists(os.path.join(csrc, headers[-1]))
+    for h in headers:
+        assert subprocess.call(query + ["-W", h, "libsamsim_hip.so"]) == 1, f"{h} is not a prerequisite of the library"

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Fill the @MARKER@ fields of DESIGN.md (the table and the paragraph of section 4 carry them while a round is in progress) from the
-committed summaries under profiles/; run after tools/collect_profiles.py.  Once filled, the markers are gone: put them back to refill."""
+committed summaries under profiles/; run after tools/collect_profiles.py.  Once filled, the markers are gone: put them back to refill.
+The table and that paragraph are the current design and stay in DESIGN.md; a round's step-by-step timings and what it tried and
+dropped go to docs/HISTORY.md by hand."""
 import json
 import re
 import sys
