@@ -197,6 +197,29 @@ MODULE mo_samsim_capi
        TYPE(samsim_profile_request), INTENT(in) :: rq
        TYPE(samsim_stat), INTENT(out) :: out(*)
      END FUNCTION
+     !> a group label per column, -1 = in no group (0-based labels below ngroups); ngroups = 0 with c_null_ptr removes the labels
+     INTEGER(c_int) FUNCTION samsim_set_groups(h, ngroups, group_of_column) BIND(C, name='samsim_set_groups')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: ngroups
+       TYPE(c_ptr), VALUE :: group_of_column             ! int32 [ncol], or c_null_ptr
+     END FUNCTION
+     !> the statistics of samsim_get_ensemble_stats per group; out(ngroups, nslots), group fastest
+     INTEGER(c_int) FUNCTION samsim_get_group_stats(h, nslots, slots, out) BIND(C, name='samsim_get_group_stats')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: nslots
+       INTEGER(c_int32_t), INTENT(in) :: slots(*)        ! enum samsim_scalar values (0-based), -1 = N_active
+       TYPE(samsim_stat), INTENT(out) :: out(*)
+     END FUNCTION
+     !> samsim_get_profile_stats over the columns with label group (0-based); out(nbins, narrays)
+     INTEGER(c_int) FUNCTION samsim_get_group_profile_stats(h, rq, group, out) BIND(C, name='samsim_get_group_profile_stats')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(samsim_profile_request), INTENT(in) :: rq
+       INTEGER(c_int32_t), VALUE :: group
+       TYPE(samsim_stat), INTENT(out) :: out(*)
+     END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')
        IMPORT

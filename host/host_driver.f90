@@ -5,7 +5,7 @@
 !!
 !! New surface the reference does not have (SURVEY.md, introduction): a namelist file `samsim.nml`
 !!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites,
-!!                 profile_bins, profile_dz, profile_origin /
+!!                 profile_bins, profile_dz, profile_origin, stats_by_site /
 !! (col0 / ncol_total: this process owns the global columns col0 .. col0+ncol-1 of an ensemble of ncol_total -- one host
 !! process per GPU, contiguous column ranges, no exchange between them, SURVEY.md section 8e)
 !!   &samsim_flags <any flag of mo_data.f90:136-155 or scalar set by mo_init> /       (overrides init(testcase))
@@ -35,6 +35,8 @@ MODULE mo_data
   INTEGER             :: profile_bins = 0    !< > 0: ensemble statistics of T, S_bu and psi_l in profile_bins depth bins at every output point
   REAL(wp)            :: profile_dz = 0._wp  !< width of a depth bin [m]
   INTEGER             :: profile_origin = 0  !< 0 depth below the ice surface, 1 height above the ice bottom
+  LOGICAL             :: stats_by_site = .FALSE.   !< with more than one site: the ensemble statistics per site as well (dat_ens_site.dat, dat_ens_profile_*_site<kk>.dat)
+  LOGICAL             :: by_site = .FALSE.   !< stats_by_site asked for and the run has more than one site: the handle carries the sites as group labels
   INTEGER             :: i_time, i_time_out
   REAL(wp)            :: fl_q_bottom = 0._wp, T_top = 0._wp, fl_sw = 0._wp, fl_rest = 0._wp, T2m = 0._wp, tank_depth = 0._wp
   INTEGER             :: N_bgc = 1
@@ -517,8 +519,77 @@ CONTAINS
     DEALLOCATE(q)
   END SUBROUTINE output_profile
 
+  !> the units of dat_ens_profile_{T,S_bu,psi_l}_site<kk>.dat: array a = 1..3 of site s = 1..nsites.  nsites is at most
+  !! SIZE(sites) = 16 (the namelist holds no more directories), so the units stay within 601..648 and <kk> within two digits.
+  INTEGER FUNCTION site_unit(a, s)
+    INTEGER, INTENT(in) :: a, s
+    site_unit = 600 + 3*(s - 1) + a
+  END FUNCTION site_unit
+
+  !> dat_ens_site.dat and dat_ens_profile_{T,S_bu,psi_l}_site<kk>.dat: opened only when the run asks for statistics by site and
+  !! has more than one site
+  SUBROUTINE output_begin_site()
+    CHARACTER(len=8), PARAMETER :: names(3) = (/ 'T       ', 'S_bu    ', 'psi_l   ' /)
+    CHARACTER(len=96) :: name
+    INTEGER :: a, s
+    IF (.NOT. by_site) RETURN
+    OPEN(55, file='./output/dat_ens_site.dat', STATUS='replace', Recl=12288)
+    IF (profile_bins <= 0) RETURN
+    DO s = 1, nsites
+       DO a = 1, 3
+          WRITE(name, '(A,A,A,I2.2,A)') './output/dat_ens_profile_', TRIM(names(a)), '_site', s, '.dat'
+          OPEN(site_unit(a, s), file=TRIM(name), STATUS='replace', Recl=64 + 74*profile_bins)
+       END DO
+    END DO
+  END SUBROUTINE output_begin_site
+
+  !> One row per output point and site in dat_ens_site.dat: the time, the 1-based site, then the row of dat_ensemble.dat for the
+  !! columns of that site (samsim_get_group_stats, all sites in one walk over each scalar); and, with profile_bins > 0, one row per
+  !! output point in each site's profile files (samsim_get_group_profile_stats, one call per site).
+  SUBROUTINE output_site(h, time)
+    TYPE(c_ptr), INTENT(in) :: h
+    REAL(wp),    INTENT(in) :: time
+    INTEGER(c_int32_t) :: slots(6)
+    TYPE(samsim_stat), ALLOCATABLE :: q(:, :)
+    TYPE(samsim_profile_request) :: rq
+    CHARACTER(len=64) :: fmt
+    INTEGER :: a, b, j, s
+    IF (.NOT. by_site) RETURN
+    slots = (/ S_THICKNESS - 1, S_THICK_SNOW - 1, S_BULK_SALIN - 1, S_FREEBOARD - 1, S_T_TOP - 1, -1 /)
+    ALLOCATE(q(nsites, 6))
+    CALL samsim_check(samsim_get_group_stats(h, 6_c_int32_t, slots, q), 'samsim_get_group_stats')
+    DO s = 1, nsites
+       WRITE(55, '(F14.1,I10,I10,24ES16.8)') time, s, q(s, 1)%count, (q(s, j)%mean, q(s, j)%min, q(s, j)%max, q(s, j)%std, j = 1, 6)
+    END DO
+    DEALLOCATE(q)
+    IF (profile_bins <= 0) RETURN
+    rq%struct_size = INT(c_sizeof(rq), c_int32_t)
+    rq%axis = SAMSIM_PROFILE_BY_DEPTH; rq%origin = INT(profile_origin, c_int32_t)
+    rq%nbins = INT(profile_bins, c_int32_t); rq%narrays = 3
+    rq%arrays = 0
+    rq%arrays(1:3) = (/ A_T - 1, A_S_BU - 1, A_PSI_L - 1 /)
+    rq%z0 = 0._wp; rq%dz = profile_dz
+    ALLOCATE(q(profile_bins, 3))
+    WRITE(fmt, '(A,I0,A)') '(F14.1,', profile_bins, '(I10,4ES16.8))'
+    DO s = 1, nsites
+       CALL samsim_check(samsim_get_group_profile_stats(h, rq, INT(s - 1, c_int32_t), q), 'samsim_get_group_profile_stats')
+       DO a = 1, 3
+          WRITE(site_unit(a, s), fmt) time, (q(b, a)%count, q(b, a)%mean, q(b, a)%min, q(b, a)%max, q(b, a)%std, b = 1, profile_bins)
+       END DO
+    END DO
+    DEALLOCATE(q)
+  END SUBROUTINE output_site
+
   SUBROUTINE output_end()
     INTEGER :: u
+    IF (by_site) THEN
+       CLOSE(55)
+       IF (profile_bins > 0) THEN
+          DO u = site_unit(1, 1), site_unit(3, nsites)
+             CLOSE(u)
+          END DO
+       END IF
+    END IF
     IF (profile_bins > 0) THEN
        CLOSE(52); CLOSE(53); CLOSE(54)
     END IF
@@ -661,7 +732,8 @@ CONTAINS
     TYPE(samsim_output_soa) :: o
     TYPE(samsim_clock)      :: clk
     REAL(c_double), ALLOCATABLE, TARGET :: olay(:, :, :), oscal(:, :), obgc(:, :, :), obot(:, :)
-    INTEGER(c_int32_t), ALLOCATABLE, TARGET :: ona(:), status(:), err_layer(:), site_of_column(:)
+    INTEGER(c_int32_t), ALLOCATABLE, TARGET :: ona(:), status(:), err_layer(:)
+    INTEGER(c_int32_t), ALLOCATABLE, TARGET :: site_of_column(:)
     INTEGER(c_int64_t), ALLOCATABLE :: err_step(:)
     INTEGER(c_int64_t) :: n, done, total, cells, colsteps
     INTEGER :: nfail, count0, count1, rate, j
@@ -690,6 +762,9 @@ CONTAINS
        DO n = 1, ncol
           site_of_column(n) = INT(MOD(col0 + n - 1, INT(nsites, c_int64_t)), c_int32_t)
        END DO
+       by_site = stats_by_site .AND. nsites > 1
+       IF (by_site) CALL samsim_check(samsim_set_groups(h, INT(nsites, c_int32_t), c_loc(site_of_column)), 'samsim_set_groups')
+       CALL output_begin_site()
        IF (perturb) THEN
           CALL sub_perturbation()
           CALL samsim_check(samsim_set_forcing_sites(h, INT(nsites, c_int32_t), INT(Length_Input, c_int32_t), fl_sw_input, &
@@ -736,6 +811,7 @@ CONTAINS
           END IF
           CALL output_ensemble(h, o%time)
           CALL output_profile(h, o%time)
+          CALL output_site(h, o%time)
           time = o%time
           thick1 = olay(1, 1, A_THICK)
           ! console progress line, mo_grotz.f90:371-381
@@ -782,7 +858,7 @@ PROGRAM SAMSIM
   CHARACTER*12000 :: description
   LOGICAL         :: have_nml
   NAMELIST /samsim_run/ testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, &
-       restart_out, sites, profile_bins, profile_dz, profile_origin
+       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site
 
   testcase    = 1
   description = 'MI355X-native batched column solver'

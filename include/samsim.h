@@ -278,6 +278,42 @@ typedef struct samsim_profile_request {
 } samsim_profile_request;
 int samsim_get_profile_stats(samsim_handle *h, const samsim_profile_request *rq, samsim_stat *out);
 
+/* Ensemble statistics per group of columns -- per forcing site, per class of the perturbation, per ocean regime -- reduced on the
+ * device.  The three entry points below were added without a change of SAMSIM_ABI_VERSION (it stays 6): they are new symbols only,
+ * no existing struct or signature changed, and a caller that wants them finds them by symbol (dlsym; a library built before them
+ * does not export them).
+ *
+ * samsim_set_groups attaches a label to every column: group_of_column[c] in [-1, ngroups), -1 = the column is in no group;
+ *   ngroups in 1..SAMSIM_MAX_GROUPS.  ngroups == 0 with NULL removes the labels.  Every label is checked on the host before any
+ *   device work: SAMSIM_ERR_ARG for a bad ngroups, a bad label or NULL with ngroups > 0, and a call that is refused leaves the
+ *   previous labels in force.  The labels live on the device as int32[ncol] and belong to the caller, as the forcing does:
+ *   samsim_set_state, samsim_set_status and stepping leave them alone, they are not part of a checkpoint (a restart sets them
+ *   again, as it sets the forcing again), samsim_destroy frees them.
+ * samsim_get_group_stats: out[nslots][ngroups], the slots of samsim_get_ensemble_stats (SAMSIM_STAT_N_ACTIVE included).  Group g
+ *   covers the columns with status == 0 and label g; per (slot, group) count, mean, min, max and the population standard
+ *   deviation, with count == 0 the other four are 0.0.  All groups of a slot are reduced in one walk over the row.
+ *   SAMSIM_ERR_ARG when no labels are set or a slot is out of range, found before any device work.
+ * samsim_get_group_profile_stats: samsim_get_profile_stats restricted to the columns with label `group` (a column with another
+ *   label or -1 behaves like a stopped one); all of that function's argument checks, in the same order, then SAMSIM_ERR_ARG when
+ *   no labels are set or group lies outside [0, ngroups).  One group per call: a request for G groups is G calls.
+ *
+ *   Statistics.  count, min and max are exact.  mean and std are formed from deviations (running and pairwise (n, mean, M2)), never
+ *     from sum v^2 - n mean^2.  No floating-point atomics, a grid fixed by ncol and ngroups, a fixed order of combination: two calls
+ *     on the same state and labels return the same bytes.
+ *   Invariance.  The order in which the values of group g are combined depends only on the positions of g's columns: relabelling
+ *     columns outside g (in other groups, or with label -1) leaves g's results unchanged, byte for byte.
+ *   A group whose columns hold identical values gives mean == min == max and std == 0.0 exactly.
+ *   With ngroups == 1 and every label 0, samsim_get_group_profile_stats(h, rq, 0, out) returns the bytes of
+ *     samsim_get_profile_stats(h, rq, out).
+ *   Like every getter the calls wait for the handle's streams; they change neither the state, the clock nor the output snapshot.
+ *   Device scratch of samsim_get_group_stats: at most SAMSIM_GROUP_SCRATCH_BYTES whatever ncol, nslots and ngroups are (every slot
+ *     reuses it); allocated on first use, kept in the handle, freed by samsim_destroy.  Only results come back to the host. */
+#define SAMSIM_MAX_GROUPS 1024
+#define SAMSIM_GROUP_SCRATCH_BYTES (16ull << 20)
+int samsim_set_groups(samsim_handle *h, int32_t ngroups, const int32_t *group_of_column);
+int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, samsim_stat *out);
+int samsim_get_group_profile_stats(samsim_handle *h, const samsim_profile_request *rq, int32_t group, samsim_stat *out);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

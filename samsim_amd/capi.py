@@ -57,6 +57,7 @@ PROFILE_MAX_BINS = 1024
 PROFILE_MAX_ARRAYS = 8
 PROFILE_AXES = {"layer": 0, "depth": 1}
 PROFILE_ORIGINS = {"top": 0, "bottom": 1}
+MAX_GROUPS = 1024           # SAMSIM_MAX_GROUPS
 
 
 class ProfileRequest(C.Structure):
@@ -182,6 +183,7 @@ class Solver:
         self._bind()
         self._chk(self._create(device), "create")
         self._out_window = (0, 1)
+        self.ngroups = 0            # groups of set_groups; 0: no labels
 
     def _create(self, device):
         f = self._f("create")
@@ -235,6 +237,15 @@ class Solver:
         f.argtypes, f.restype = [vp, i64, C.c_int32], C.c_int
         f = self._f("get_profile_stats")
         f.argtypes, f.restype = [vp, C.POINTER(ProfileRequest), C.c_void_p], C.c_int
+        # the per-group statistics came as new symbols under ABI 6: a library of ABI 6 built before them (an A/B build of an older
+        # commit) still loads, and a call of one of them fails with the missing symbol's name
+        group_sig = {"set_groups": [vp, C.c_int32, C.POINTER(C.c_int32)],
+                     "get_group_stats": [vp, C.c_int32, C.POINTER(C.c_int32), C.c_void_p],
+                     "get_group_profile_stats": [vp, C.POINTER(ProfileRequest), C.c_int32, C.c_void_p]}
+        for n, a in group_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
 
     # -- API
     def set_forcing(self, fl_sw, fl_lw, T2m, precip, dT2m=None, precip_scale=None):
@@ -395,19 +406,52 @@ class Solver:
         self._chk(self._f("get_ensemble_stats")(self._h, len(names), slots, out), "get_ensemble_stats")
         return {n: out[i] for i, n in enumerate(names)}
 
-    def profile_stats_raw(self, rq: ProfileRequest) -> np.ndarray:
-        """samsim_get_profile_stats with the request as given (no checks on this side): structured array [narrays][nbins]"""
+    def set_groups_raw(self, ngroups, labels):
+        """samsim_set_groups with the arguments as given (no checks on this side): labels an int32 array [ncol] or None"""
+        self._chk(self._f("set_groups")(self._h, ngroups, _ip(labels) if labels is not None else None), "set_groups")
+        self.ngroups = int(ngroups) if labels is not None else 0
+
+    def set_groups(self, labels, ngroups=None):
+        """a group label per column, -1 = in no group (samsim_set_groups); ngroups defaults to max(label) + 1; set_groups(None)
+        removes the labels"""
+        if labels is None:
+            return self.set_groups_raw(0, None)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        assert lab.shape == (self.ncol,)
+        if ngroups is None:
+            ngroups = int(lab.max()) + 1
+            if ngroups < 1:
+                raise ValueError("every label is -1: no group to count; pass ngroups, or set_groups(None) to remove the labels")
+        self.set_groups_raw(int(ngroups), lab)
+
+    def group_stats(self, names):
+        """{name: structured array [ngroups] with fields count, mean, min, max, std} over the columns without a STOP code, per
+        group of set_groups; names from SCALARS or "N_active" (samsim_get_group_stats)"""
+        names = list(names)
+        ng = self.ngroups
+        slots = (C.c_int32 * len(names))(*[-1 if n == "N_active" else S[n] for n in names])
+        out = np.zeros((len(names), max(1, ng)), dtype=STAT_DTYPE)
+        self._chk(self._f("get_group_stats")(self._h, len(names), slots, out.ctypes.data), "get_group_stats")
+        return {n: out[i] for i, n in enumerate(names)}
+
+    def profile_stats_raw(self, rq: ProfileRequest, group=None) -> np.ndarray:
+        """samsim_get_profile_stats -- with group: samsim_get_group_profile_stats -- with the request as given (no checks on this
+        side): structured array [narrays][nbins]"""
         out = np.zeros((max(0, min(rq.narrays, PROFILE_MAX_ARRAYS)), max(0, min(rq.nbins, PROFILE_MAX_BINS))), dtype=STAT_DTYPE)
         buf = np.zeros(max(1, out.size), dtype=STAT_DTYPE)
-        self._chk(self._f("get_profile_stats")(self._h, C.byref(rq), buf.ctypes.data), "get_profile_stats")
+        if group is None:
+            self._chk(self._f("get_profile_stats")(self._h, C.byref(rq), buf.ctypes.data), "get_profile_stats")
+        else:
+            self._chk(self._f("get_group_profile_stats")(self._h, C.byref(rq), int(group), buf.ctypes.data), "get_group_profile_stats")
         out.ravel()[:] = buf[:out.size]
         return out
 
-    def profile_stats(self, names, axis="layer", origin="top", nbins=None, z0=0.0, dz=None):
+    def profile_stats(self, names, axis="layer", origin="top", nbins=None, z0=0.0, dz=None, group=None):
         """{name: structured array [nbins] with fields count, mean, min, max, std} over the columns without a STOP code
         (samsim_get_profile_stats): names from ARRAYS; axis "layer" (bin b = layer b+1 from the top, or N_active-b from the
         bottom; nbins defaults to nlayer) or "depth" (bins [z0 + b dz, z0 + (b+1) dz) in metres below the ice surface or above
-        the ice bottom; nbins and dz are required)"""
+        the ice bottom; nbins and dz are required); group: only the columns with that label of set_groups
+        (samsim_get_group_profile_stats)"""
         names = list(names)
         if axis == "depth" and (nbins is None or dz is None):
             raise ValueError("axis='depth' needs nbins and dz")
@@ -419,7 +463,7 @@ class Solver:
         for i, n in enumerate(names[:PROFILE_MAX_ARRAYS]):
             rq.arrays[i] = A[n]
         rq.z0, rq.dz = float(z0), float(0.0 if dz is None else dz)
-        out = self.profile_stats_raw(rq)
+        out = self.profile_stats_raw(rq) if group is None else self.profile_stats_raw(rq, group)
         return {n: out[i] for i, n in enumerate(names)}
 
     def run_to_output(self) -> Output:

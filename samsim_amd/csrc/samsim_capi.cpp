@@ -15,12 +15,14 @@
 #include <vector>
 
 #include "samsim_device.h"
+#include "samsim_groups.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
-// samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS)
-extern "C" hipError_t samsim_launch_profile(const double *lay, const int32_t *n_active, const int32_t *status, long long ncol, int N,
-                                            int axis, int origin, int array, int b0, int nb, int nbins, double z0, double dz,
-                                            ProfPartial *part, samsim_stat *out, hipStream_t stream);
+// samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS) over every column
+// (labels null) or over the columns with label `group`
+extern "C" hipError_t samsim_launch_profile(const double *lay, const int32_t *n_active, const int32_t *status, const int32_t *labels,
+                                            int group, long long ncol, int N, int axis, int origin, int array, int b0, int nb, int nbins,
+                                            double z0, double dz, ProfPartial *part, samsim_stat *out, hipStream_t stream);
 
 namespace {
 
@@ -64,6 +66,9 @@ struct samsim_handle {
   int32_t *flags = nullptr;    // COLF_* per column
   void *d_stat = nullptr;      // block partials of samsim_get_ensemble_stats
   void *d_prof = nullptr;      // samsim_get_profile_stats: the waves' partials of one pass, then the results (kProfScratch bytes)
+  int32_t *groups = nullptr;   // [ncol] group label of each column (samsim_set_groups), owned by the caller as the forcing is
+  int32_t ngroups = 0;         // 0: no labels
+  void *d_group = nullptr;     // samsim_get_group_stats: the waves' partials of one slot, then its results (kGroupScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -196,6 +201,13 @@ constexpr size_t kProfPartBytes = sizeof(ProfPartial) * DEV_PROF_GRID * DEV_PROF
 constexpr size_t kProfScratch = kProfPartBytes + sizeof(samsim_stat) * SAMSIM_PROFILE_MAX_ARRAYS * SAMSIM_PROFILE_MAX_BINS;
 static_assert(kProfScratch <= SAMSIM_PROFILE_SCRATCH_BYTES && SAMSIM_PROFILE_SCRATCH_BYTES <= (64ull << 20), "profile scratch bound of samsim.h");
 static_assert(SAMSIM_PROFILE_MAX_BINS == SAMSIM_MAX_NLAYER, "a layer-axis request may ask for every layer");
+
+// device scratch of samsim_get_group_stats: the partials of one slot (every slot reuses them), then the results of one slot
+constexpr size_t kGroupPartBytes = sizeof(GroupPartial) * DEV_GROUP_PART_ENTRIES;
+constexpr size_t kGroupScratch = kGroupPartBytes + sizeof(samsim_stat) * SAMSIM_MAX_GROUPS;
+static_assert(kGroupScratch <= SAMSIM_GROUP_SCRATCH_BYTES, "group scratch bound of samsim.h");
+static_assert(DEV_GROUP_PART_ENTRIES >= SAMSIM_MAX_GROUPS, "at least one wave at the largest number of groups");
+static_assert(sizeof(GroupPartial) * SAMSIM_MAX_GROUPS <= (64u << 10), "a wave's table of every group fits the LDS of a workgroup");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -440,6 +452,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->lay); (void)hipFree(h->scal); (void)hipFree(h->n_active); (void)hipFree(h->status);
   (void)hipFree(h->err_layer); (void)hipFree(h->err_step); (void)hipFree(h->work);
   (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
+  (void)hipFree(h->groups); (void)hipFree(h->d_group);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
   (void)hipFree(h->ocean_dflq); (void)hipFree(h->ocean_sbu);
@@ -860,7 +873,8 @@ int samsim_get_ensemble_stats(samsim_handle *h, int32_t nslots, const int32_t *s
   return SAMSIM_OK;
 }
 
-int samsim_get_profile_stats(samsim_handle *h, const samsim_profile_request *rq, samsim_stat *out) {
+// samsim_get_profile_stats over every column (labels null) or over the columns with label `group` (samsim_get_group_profile_stats)
+static int profile_stats(samsim_handle *h, const samsim_profile_request *rq, bool grouped, int32_t group, samsim_stat *out) {
   // every check of the request first: nothing below touches the device before the request is known to be good
   if (!h || !rq || !out) return SAMSIM_ERR_ARG;
   if (rq->struct_size != (int32_t)sizeof(samsim_profile_request)) return SAMSIM_ERR_ABI;
@@ -872,20 +886,77 @@ int samsim_get_profile_stats(samsim_handle *h, const samsim_profile_request *rq,
   for (int i = 0; i < rq->narrays; ++i)
     if (rq->arrays[i] < 0 || rq->arrays[i] >= SAMSIM_NARR) return SAMSIM_ERR_ARG;
   if (depth && (!std::isfinite(rq->z0) || !std::isfinite(rq->dz) || rq->z0 < 0.0 || !(rq->dz > 0.0))) return SAMSIM_ERR_ARG;
+  if (grouped && (!h->groups || group < 0 || group >= h->ngroups)) return SAMSIM_ERR_ARG;
   int rc = use(h);
   if (rc) return rc;
   if (!h->d_prof) HIPCHK(hipMalloc(&h->d_prof, kProfScratch));
   ProfPartial *d_part = (ProfPartial *)h->d_prof;
   samsim_stat *d_out = (samsim_stat *)((char *)h->d_prof + kProfPartBytes);
+  const int32_t *labels = grouped ? h->groups : nullptr;
   // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
   // the next pass writes them
   for (int i = 0; i < rq->narrays; ++i)
     for (int b0 = 0; b0 < rq->nbins; b0 += DEV_PROF_BINS) {
       const int nb = rq->nbins - b0 < DEV_PROF_BINS ? rq->nbins - b0 : DEV_PROF_BINS;
-      HIPCHK(samsim_launch_profile(h->lay, h->n_active, h->status, h->ncol, h->cfg.nlayer, rq->axis, rq->origin, rq->arrays[i], b0, nb,
-                                   rq->nbins, depth ? rq->z0 : 0.0, depth ? rq->dz : 1.0, d_part, d_out + (size_t)i * rq->nbins + b0, h->stream));
+      HIPCHK(samsim_launch_profile(h->lay, h->n_active, h->status, labels, group, h->ncol, h->cfg.nlayer, rq->axis, rq->origin,
+                                   rq->arrays[i], b0, nb, rq->nbins, depth ? rq->z0 : 0.0, depth ? rq->dz : 1.0, d_part,
+                                   d_out + (size_t)i * rq->nbins + b0, h->stream));
     }
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_stat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_get_profile_stats(samsim_handle *h, const samsim_profile_request *rq, samsim_stat *out) {
+  return profile_stats(h, rq, false, 0, out);
+}
+
+int samsim_get_group_profile_stats(samsim_handle *h, const samsim_profile_request *rq, int32_t group, samsim_stat *out) {
+  return profile_stats(h, rq, true, group, out);
+}
+
+int samsim_set_groups(samsim_handle *h, int32_t ngroups, const int32_t *group_of_column) {
+  // every check first: a call that is refused leaves the previous labels in force
+  if (!h) return SAMSIM_ERR_ARG;
+  const bool clear = ngroups == 0 && !group_of_column;
+  if (!clear) {
+    if (ngroups < 1 || ngroups > SAMSIM_MAX_GROUPS || !group_of_column) return SAMSIM_ERR_ARG;
+    for (long long c = 0; c < h->ncol; ++c)
+      if (group_of_column[c] < -1 || group_of_column[c] >= ngroups) return SAMSIM_ERR_ARG;
+  }
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the new labels are complete on the device before the handle sees them
+  int32_t *g = nullptr;
+  if (!clear) {
+    const bool ok = hip_ok(dalloc(&g, (size_t)h->ncol), "hipMalloc groups") &&
+                    hip_ok(hipMemcpy(g, group_of_column, sizeof(int32_t) * (size_t)h->ncol, hipMemcpyHostToDevice), "hipMemcpy groups");
+    if (!ok) { (void)hipFree(g); return SAMSIM_ERR_HIP; }
+  }
+  (void)hipFree(h->groups);
+  h->groups = g;
+  h->ngroups = clear ? 0 : ngroups;
+  return SAMSIM_OK;
+}
+
+int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, samsim_stat *out) {
+  if (!h || nslots < 0 || (nslots > 0 && (!slots || !out))) return SAMSIM_ERR_ARG;
+  if (!h->groups) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < nslots; ++i)
+    if (slots[i] != SAMSIM_STAT_N_ACTIVE && (slots[i] < 0 || slots[i] >= SAMSIM_NSCAL)) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  if (!h->d_group) HIPCHK(hipMalloc(&h->d_group, kGroupScratch));
+  GroupPartial *d_part = (GroupPartial *)h->d_group;
+  samsim_stat *d_out = (samsim_stat *)((char *)h->d_group + kGroupPartBytes);
+  const size_t nc = (size_t)h->ncol, ng = (size_t)h->ngroups;
+  // one pass per slot, all on the handle's stream: a slot's results have left the scratch before the next slot's merge writes them
+  for (int i = 0; i < nslots; ++i) {
+    const double *row = (slots[i] == SAMSIM_STAT_N_ACTIVE) ? nullptr : h->scal + (size_t)slots[i] * nc;
+    HIPCHK(samsim_launch_group_stats(row, h->n_active, h->status, h->groups, h->ncol, h->ngroups, d_part, d_out, h->stream));
+    HIPCHK(hipMemcpyAsync(out + (size_t)i * ng, d_out, sizeof(samsim_stat) * ng, hipMemcpyDeviceToHost, h->stream));
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }

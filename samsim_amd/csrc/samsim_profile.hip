@@ -105,25 +105,29 @@ __device__ __forceinline__ void store_partials(ProfPartial *part, int lane, cons
   part[(size_t)blockIdx.x * DEV_PROF_BINS + lane] = p;
 }
 
-// the lane's column of block blk: its number of active layers, 0 for a column that stopped or lies beyond ncol
-__device__ __forceinline__ int active_layers(const int32_t *n_active, const int32_t *status, long long ncol, long long blk, int lane, int N) {
+// the lane's column of block blk: its number of active layers, 0 for a column that stopped, lies beyond ncol or -- with a label row
+// (samsim_get_group_profile_stats) -- carries another label than `group`: such a column behaves like a stopped one
+__device__ __forceinline__ int active_layers(const int32_t *n_active, const int32_t *status, const int32_t *labels, int group, long long ncol,
+                                             long long blk, int lane, int N) {
   const long long col = blk * 64 + lane;
   if (col >= ncol || status[col] != 0) return 0;
+  if (labels && labels[col] != group) return 0;
   const int na = n_active[col];
   return na < 0 ? 0 : (na > N ? N : na);
 }
 
 // ---- layer axis: bin b holds layer b+1 (from the top) or layer N_active-b (from the bottom); bins [b0, b0+nb)
 __global__ void __launch_bounds__(64) profile_layer_kernel(const double *__restrict__ lay, const int32_t *__restrict__ n_active,
-                                                           const int32_t *__restrict__ status, long long ncol, int N, int origin,
-                                                           int array, int b0, int nb, ProfPartial *__restrict__ part) {
+                                                           const int32_t *__restrict__ status, const int32_t *__restrict__ labels,
+                                                           int group, long long ncol, int N, int origin, int array, int b0, int nb,
+                                                           ProfPartial *__restrict__ part) {
   __shared__ double tile[DEV_PROF_BINS * kTileStride];
   __shared__ unsigned long long smask[64];
   const int lane = threadIdx.x;
   const long long nblk = (ncol + 63) / 64;
   Run run{0, 0.0, 0.0, 0.0, 0.0};
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const int na = active_layers(n_active, status, ncol, blk, lane, N);
+    const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
     const int kmax = wave_max(na);
     const double *base = lay + DEV_LAY_INDEX(0, 0, blk * 64 + lane, N, ncol);   // the lane's element of array 0, layer 1
     unsigned long long mask = 0;
@@ -162,9 +166,9 @@ __global__ void __launch_bounds__(64) profile_layer_kernel(const double *__restr
 // ---- depth axis: bin b is [z0 + b dz, z0 + (b+1) dz) below the ice surface (from the top) or above the ice bottom; a column's
 // value in a bin is the overlap-weighted mean of its layers there (samsim.h); bins [b0, b0+nb)
 __global__ void __launch_bounds__(64) profile_depth_kernel(const double *__restrict__ lay, const int32_t *__restrict__ n_active,
-                                                           const int32_t *__restrict__ status, long long ncol, int N, int origin,
-                                                           int array, int b0, int nb, int lead, double z0, double dz,
-                                                           ProfPartial *__restrict__ part) {
+                                                           const int32_t *__restrict__ status, const int32_t *__restrict__ labels,
+                                                           int group, long long ncol, int N, int origin, int array, int b0, int nb,
+                                                           int lead, double z0, double dz, ProfPartial *__restrict__ part) {
   __shared__ double tile[DEV_PROF_BINS * kTileStride];
   __shared__ unsigned long long smask[64];
   const int lane = threadIdx.x;
@@ -172,7 +176,7 @@ __global__ void __launch_bounds__(64) profile_depth_kernel(const double *__restr
   const bool top = origin == SAMSIM_PROFILE_FROM_TOP;
   Run run{0, 0.0, 0.0, 0.0, 0.0};
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const int na = active_layers(n_active, status, ncol, blk, lane, N);
+    const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
     const int kmax = wave_max(na);
     const double *base = lay + DEV_LAY_INDEX(0, 0, blk * 64 + lane, N, ncol);   // the lane's element of array 0, layer 1
     double H = 0.0;
@@ -272,17 +276,19 @@ __global__ void __launch_bounds__(64) profile_merge_kernel(const ProfPartial *__
 }  // namespace
 
 // One pass: array `array`, bins [b0, b0 + nb) of the request's nbins with nb <= DEV_PROF_BINS, results to out[0 .. nb).  part holds DEV_PROF_GRID *
-// DEV_PROF_BINS partials and is reused by the next pass on the same stream.
-extern "C" hipError_t samsim_launch_profile(const double *lay, const int32_t *n_active, const int32_t *status, long long ncol, int N,
-                                            int axis, int origin, int array, int b0, int nb, int nbins, double z0, double dz,
-                                            ProfPartial *part, samsim_stat *out, hipStream_t stream) {
+// DEV_PROF_BINS partials and is reused by the next pass on the same stream.  labels: null (every column counts), or the [ncol] label row
+// of samsim_set_groups, of which only the columns with label `group` count.
+extern "C" hipError_t samsim_launch_profile(const double *lay, const int32_t *n_active, const int32_t *status, const int32_t *labels,
+                                            int group, long long ncol, int N, int axis, int origin, int array, int b0, int nb, int nbins,
+                                            double z0, double dz, ProfPartial *part, samsim_stat *out, hipStream_t stream) {
   const long long nblk = (ncol + 63) / 64;
   const int grid = (int)(nblk < DEV_PROF_GRID ? nblk : DEV_PROF_GRID);
   if (axis == SAMSIM_PROFILE_BY_LAYER)
-    hipLaunchKernelGGL(profile_layer_kernel, dim3(grid), dim3(64), 0, stream, lay, n_active, status, ncol, N, origin, array, b0, nb, part);
+    hipLaunchKernelGGL(profile_layer_kernel, dim3(grid), dim3(64), 0, stream, lay, n_active, status, labels, group, ncol, N, origin, array, b0,
+                       nb, part);
   else
-    hipLaunchKernelGGL(profile_depth_kernel, dim3(grid), dim3(64), 0, stream, lay, n_active, status, ncol, N, origin, array, b0, nb,
-                       origin == SAMSIM_PROFILE_FROM_TOP ? b0 > 0 : b0 + nb < nbins, z0, dz, part);
+    hipLaunchKernelGGL(profile_depth_kernel, dim3(grid), dim3(64), 0, stream, lay, n_active, status, labels, group, ncol, N, origin, array,
+                       b0, nb, origin == SAMSIM_PROFILE_FROM_TOP ? b0 > 0 : b0 + nb < nbins, z0, dz, part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(profile_merge_kernel, dim3(1), dim3(64), 0, stream, part, grid, nb, out);
