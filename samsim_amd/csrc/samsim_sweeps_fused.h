@@ -58,11 +58,12 @@ __device__ __forceinline__ Expelled expulsion(double phi, double thick, double m
 // Permeability + Rayleigh number of layer k from its T, phi (Expulsion evaluated in registers).  Only PHI (by the caller)
 // and ray are stored: the down sweep re-evaluates Expulsion from PHI, m and thick (same inputs, same operations) and
 // writes the psi arrays itself, which is cheaper than handing psi_s, psi_l, psi_g and V_ex over through HBM.
+// (S_br_T: S_br_clamped(T, S_bu) where the caller has it already -- getT_chain's S_br_out)
 template <class K>
 __device__ __forceinline__ void s1_layer(Col &c, const Ctx &x, int k, int Na, bool do_ray, double T, double phi, double S_bu,
-                                         double m, double thick, double rth, RayScan &r, bool sparse_rows = false) {
+                                         double m, double thick, double rth, RayScan &r, bool sparse_rows = false, const double *S_br_T = nullptr) {
   const samsim_config &g = x.p->cfg;
-  const double S_br = S_br_clamped(x.salt, T, S_bu);
+  const double S_br = S_br_T ? *S_br_T : S_br_clamped(x.salt, T, S_bu);
   const Expelled e = expulsion(phi, thick, m, rth);
   r.min_psi_s = dmin(r.min_psi_s, e.psi_s);
   r.buoy_s += e.psi_s * thick;
@@ -174,6 +175,18 @@ __device__ __forceinline__ double heat_conductance(double psi_s, double psi_l, d
 }
 __device__ __forceinline__ double heat_flux_between(double dT, double g_a, double g_b) {
   return quot(dT * (g_a * g_b), g_a + g_b);
+}
+
+// A copy of v in registers of its own, which the optimiser cannot fold back into v (to the compiler the move is an opaque
+// instruction with one result): ends the life of the registers v sits in.  See the trip loop of sweep_down_fused.
+__device__ __forceinline__ double out_of_row(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double r;
+  asm volatile("v_mov_b64 %0, %1" : "=v"(r) : "v"(v));
+  return r;
+#else
+  return v;
+#endif
 }
 
 // ---------------------------------------------------------------- D: fused down sweep (P2 + P3), top -> bottom
@@ -318,7 +331,7 @@ __device__ __forceinline__ void sweep_down_fused(Col &c, const Ctx &x, bool stor
     }
 #endif
     const double SA = S_abs, mA = m;     // S_bu = SA / mA: refreshed bulk salinity, mo_grotz.f90:333-335 (formed where it is read)
-    T_up = T; S_br_up = S_br; S_abs_up = S_abs;
+    S_br_up = S_br;                      // (T_up and S_abs_up, the other two values mass_transfer #1 of the next layer sees: at the end of the layer)
     flm_j = flm_next;
     // Thin-snow coupling (mo_grotz.f90:418-420) sits between expulsion / mass_transfer and everything below in the reference.  It
     // reads and writes layer 1 only, and layer 1 is through with the expulsion here (its own flux and the one into layer 2 are
@@ -384,6 +397,11 @@ __device__ __forceinline__ void sweep_down_fused(Col &c, const Ctx &x, bool stor
       }
     }
     sum_after += S_abs;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (the two sums are formed here, not wherever the scheduler finds room for them in the following layers: a deferred addition
+    // keeps S_abs of this layer alive in the registers of its request buffer, past the point where the buffer is requested into again)
+    asm volatile("" : "+v"(sum_before), "+v"(sum_after));
+#endif
     if (!LAST && !FIRST) { ISA_MARK("D_LAYER_C"); }
     // ---- C(j-1): layer j-1 receives from layer j (fl_m(j) = fl_up(j-1)) and gives to j-2 (fl_m(j-1) = fl_up(j-2))
     if (j > 1) {
@@ -417,7 +435,11 @@ __device__ __forceinline__ void sweep_down_fused(Col &c, const Ctx &x, bool stor
       flup_pp = prev.flup;
     }
     g_up = gj; flq_up = flq;
-    prev.T = Tl; prev.SA = SA; prev.mA = mA; prev.S_abs = S_abs; prev.H_abs = H_abs; prev.m = m; prev.flup = flup; prev.ch = ch;
+    // T, and H_abs, SA and S_abs wherever no brine moved, are still the values the row was loaded with, in the registers of its
+    // request buffer: out_of_row() takes them out, so that the buffer is free for the next request (see the trip loop below)
+    T_up = out_of_row(T); S_abs_up = out_of_row(SA);
+    prev.T = FIRST ? out_of_row(Tl) : T_up; prev.SA = S_abs_up; prev.mA = mA; prev.S_abs = out_of_row(S_abs); prev.H_abs = out_of_row(H_abs);
+    prev.m = m; prev.flup = flup; prev.ch = ch;
     if (!LAST && !FIRST) { ISA_MARK("D_LAYER_END"); }
     ST_MARK(ST_D_B);
   };
@@ -467,6 +489,13 @@ __device__ __forceinline__ void sweep_down_fused(Col &c, const Ctx &x, bool stor
   // the registers the next trip expects it in, behind `s_waitcnt vmcnt(3..0)`: a full drain, the second layer's own stores
   // included, every other layer.)  A column whose interior layers end inside a trip, and the 0-2 layers a stretch has left
   // over, take single-layer steps that do copy their buffer (at most two per column and six per wave and sweep).
+  // A row's VALUES live for four layer bodies, though, not three: requested two layers ahead, `raw` for a layer -- and then T,
+  // and H_abs / S_abs where no brine moved, go on as `prev`, T_up and S_abs_up until C and A of the next layer, in the registers
+  // they were loaded into.  A buffer that is busy for four layers does not go round in three: the third request of the trip
+  // went into registers of its own and was copied into the buffer on the back edge, while still outstanding, behind
+  // `s_waitcnt vmcnt(0)` -- the last full drain of the trip.  So the layer ends by moving what lives on out of the row
+  // (out_of_row: at most four 64-bit moves, behind a wait the layer has had anyway) and by forming its two salt sums where the
+  // source has them: the buffer is then dead when it is requested into again, and the back edge carries no copy and no wait.
   {
     const int b0 = g.n_top, b1 = g.n_top + g.n_middle;
     Ld ahead3 = ahead;
@@ -619,12 +648,12 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
     double S_abs = S_k;
     double S_bu, H;
     per_mass(S_abs, H_abs, m, S_bu, H);
-    double T, phi = 0.0;
+    double T, phi = 0.0, S_br_T = 0.0;   // S_br_T: the liquidus salinity at T, formed once for phi and for the first sweep of the next step
     if (!TOP) { ISA_MARK("U_GETT_BEGIN"); }
     ST_MARK(ST_U_HEAD);
 #if SAMSIM_STAMPS == 2
     int evals = 1;
-    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi, &evals) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi, &evals);
+    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi, &evals) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi, &evals, LITE ? nullptr : &S_br_T);
     {
       const bool was_odd = (evals >> 30) & 1;
       const int redo = (evals >> 16) & 0x3fff;
@@ -637,7 +666,7 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
     { int tot = 0; unsigned long long mk = __ballot(1); while (mk) { const int ln = __ffsll((long long)mk) - 1; tot += __builtin_amdgcn_readlane(evals, ln); mk &= mk - 1; }
       ST_COUNT(CT_NEWTON_LANE, (unsigned long long)tot); }
 #else
-    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi);
+    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi, nullptr, LITE ? nullptr : &S_br_T);
 #endif
     if (!TOP) { ISA_MARK("U_GETT_END"); }
     ST_MARK(ST_U_GETT);
@@ -652,7 +681,7 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
       // (a clamped salt mass changes S_bu and therefore T: such a column is left to the full sweep, flagged after the loop -- a
       // read-modify-write of the column's flag word inside the loop is one more value for the allocator to spill there)
       neg_salt = neg_salt || (S_abs < 0.0);
-      s1_layer<K>(c, x, k, Na, do_ray, T, phi, S_bu, m, th_k, rth_k, r, true);
+      s1_layer<K>(c, x, k, Na, do_ray, T, phi, S_bu, m, th_k, rth_k, r, true, &S_br_T);
     }
     ST_MARK(ST_U_TAIL);
   };

@@ -203,8 +203,12 @@ __device__ __forceinline__ int getT(const Salt &s, double H, double S_bu, double
 // replaced by the freezing temperature inside the loop, exactly where the general routine does it, instead of sending the lane
 // through the general routine afterwards -- near 0 C a third of the layers of a wave hold such a lane, and each cost the wave a
 // second, slower iteration from the start.  The winter sweeps keep the loop without it (three registers less in their layer loop).
+// S_br_out (the fused up sweep's full layers): the clamped liquidus salinity at the temperature returned, which the first sweep of the
+// next step needs as well, is formed ONCE, after the redo, and handed out: a lane that was not redone keeps the loop's temperature, so
+// its phi comes from the same operands as before, and the polynomial is not evaluated a second time behind the redo.
 template <bool WARM = false>
-__device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, double T_in, double &T_out, double &phi_out, int *evals = nullptr) {
+__device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, double T_in, double &T_out, double &phi_out, int *evals = nullptr,
+                                          double *S_br_out = nullptr) {
   const double Tl = T_liquid(H);
   const bool mushy = S_br_clamped(s, Tl, S_bu) > S_bu && S_bu > 0.001;
   const double A0 = -latent_heat - H, LS = latent_heat * S_bu;
@@ -246,7 +250,7 @@ __device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, 
   }
   const bool odd = odd_i != 0;
   ISA_MARK("NEWTON_LOOP_END");
-  double phi = 1.0 - quot(S_bu, S_br_clamped(s, T, S_bu));
+  double phi = S_br_out ? 0.0 : 1.0 - quot(S_bu, S_br_clamped(s, T, S_bu));
   int rc = 0;
   if (odd) {
     phi = phi_out;
@@ -257,6 +261,11 @@ __device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, 
 #if SAMSIM_STAMPS == 2
     if (evals) *evals += ((*evals - ev0) << 16) | (1 << 30);   // (decoded by the caller: redone by the general routine, its evaluations)
 #endif
+  }
+  if (S_br_out) {
+    const double S_br_T = S_br_clamped(s, T, S_bu);
+    if (!odd) phi = 1.0 - quot(S_bu, S_br_T);
+    *S_br_out = S_br_T;
   }
   T_out = T;
   phi_out = phi;
