@@ -167,7 +167,11 @@ int samsim_set_ocean(samsim_handle *h, const double *dfl_q_bottom_col, const dou
 
 /* initial state of init(testcase) (mo_init.f90:141-1978) or a checkpoint; col0 and s->ncol select a window.
  * The two perturbation slots SAMSIM_S_DT2M / SAMSIM_S_PRECIP_SCALE are owned by samsim_set_forcing: set_state
- * ignores them, get_state returns them. */
+ * ignores them, get_state returns them.
+ * The health check at the end of a step clamps S_abs >= 0 over the active layers (mo_grotz.f90:812-818).  The state samsim_get_state
+ * returns after a step is the clamped one, as the reference holds it between two steps; a state that samsim_set_state uploads is
+ * taken as it is, as the reference takes its initial state: a negative S_abs in it enters the first step (where the expelled brine's
+ * mass_transfer may absorb it, or gravity drainage's MINVAL(S_abs) test stops the column with 1337). */
 /* Both move the layer arrays of the window through a device staging buffer in pieces of at most SAMSIM_STAGE_MAX_BYTES: the
  * buffer never holds more, whatever the window. */
 #define SAMSIM_STAGE_MAX_BYTES (256ull << 20)
@@ -201,7 +205,38 @@ int samsim_set_output_window(samsim_handle *h, int64_t col0, int64_t ncols);
 int samsim_get_output(samsim_handle *h, samsim_output_soa *o);
 
 /* the reference's STOP codes: status[c] = 0 or code; step/layer of first failure.  Every code is one of the
- * reference's own (16, 99, 345, 431, 1337, 7889, 9876, 21234, ...): the library stops no column the reference would not. */
+ * reference's own (16, 99, 345, 431, 1337, 7889, 9876, 21234, ...): the library stops no column the reference would not.
+ *
+ * step[c] is the 1-based index i of the time step in which the column stopped (clock.step + 1 of that step).  A stopped column is
+ * frozen: no later step changes its state, its status or its share of samsim_get_work, and the ensemble statistics leave it out.
+ *
+ * layer[c] is the library's own notion (the reference prints none).  It is the layer k where the reference's test sits inside a
+ * layer loop or names a layer, and 0 where the reference tests a quantity of the whole column or of the snow:
+ *
+ *   code   site of the reference                                              layer
+ *   99     getT of a layer, first or second sweep (mo_grotz.f90:297-307, 592-598)   k; several failing layers in one sweep: the
+ *                                                                              LARGEST k -- the sweeps run from N_active up to 1,
+ *                                                                              and that is where the reference aborts
+ *   99     getT of layer 1 at the head of a step whose other layers were swept by the step before     1
+ *   99     either getT of the thin-snow coupling, snow_coupling (mo_snow.f90:61-104), of the snow or of layer 1:      1
+ *   16     the exchange loop of the thin-snow coupling does not converge        1
+ *   99     getT of the snow in snow_thermo / snow_thermo_meltwater (mo_snow.f90:212-454)   0
+ *   345    snow_thermo: psi_s_snow + psi_l_snow                                  0
+ *   9876   snow_thermo: psi_g_snow < 0                                           0
+ *   21234  gravity drainage: S_abs(k) < 0 after the loss of layer k (mo_grav_drain.f90:144-170)    k; several: the SMALLEST k (that
+ *                                                                              loop runs from layer 1 to N_active - 1)
+ *   1337   gravity drainage: MINVAL(S_abs) < 0 (mo_grav_drain.f90:197)           0
+ *   431    energy balance of sub_heat_fluxes (mo_heat_fluxes.f90:265-310)        0
+ *   9876   flush3: m(1) flushed away (mo_flush.f90)                              1
+ *   9876   flush4: MINVAL(S_abs) < 0 (mo_flush.f90:253-296)                      0
+ *   7889   top_melt: SUM(thick) (mo_layer_dynamics.f90:191-327)                  0
+ *   1337   health check at the end of the step: MINVAL(psi_s) < 0 (mo_grotz.f90:808-819)   0
+ *
+ * A column that meets two tests in one step reports the one the reference reaches first; within sub_heat_fluxes and after it
+ * the order is: thin-snow coupling (99, 16), energy balance (431), second getT sweep (99).
+ * The coupling reports layer 1 for both of its getT calls because it runs them as one pair and keeps one return code.
+ * STOP 431 fires only through round-off (an enthalpy whose ulp exceeds 1e-5 W * dt): the reference compares two column sums, the
+ * library sums per-layer differences, so on such a column the two may stop in different steps (tests/stop_seeds.py). */
 int samsim_get_status(samsim_handle *h, int32_t *status, int64_t *step, int32_t *layer);
 /* restart only: puts back what samsim_get_status returned for the columns [col0, col0+ncols) (samsim_set_state clears the
  * status of the columns it uploads), so that a column frozen by a STOP code stays frozen -- and reported -- after a

@@ -488,7 +488,7 @@ static void fl_grav_drain(column *c) {
 
   if (g->grav_heat_flag == 2) H_abs[Na] = H_abs[Na] + heat_loss - fl_up[Na] * c_l * g->T_bottom;
 
-  for (k = 1; k <= N; k++) if (S_abs[k] < 0.0) STOP(1337, k);                        /* :197-200 */
+  for (k = 1; k <= N; k++) if (S_abs[k] < 0.0) STOP(1337, 0);                        /* :197-200: MINVAL(S_abs), no layer */
 }
 
 /* fl_grav_drain_simple, mo_grav_drain.f90:218-278 (grav_flag 3): Rayleigh numbers as above, then every layer above the
@@ -547,7 +547,8 @@ double oracle_func_k_snow(double m_snow, double thick_snow) {
 /* snow_coupling, mo_snow.f90:61-104.
  * The reference passes T_snow (resp. T) as BOTH the INTENT(in) guess T_in and the INTENT(out) result of getT
  * (:74-75 etc.).  Arguments are by reference, so getT's first statement `T = H/c_l` also overwrites T_in:
- * the Newton first guess of these calls is H/c_l, not the previous temperature. */
+ * the Newton first guess of these calls is H/c_l, not the previous temperature.
+ * A STOP 99 of either call of the coupling is reported with layer 1, like its STOP 16 (include/samsim.h, samsim_get_status). */
 static void getT_aliased(column *c, double H, double S_bu, double *T, double *phi, int tag) {
   getT(c, H, S_bu, H / c_l, T, phi, tag);
 }
@@ -560,18 +561,18 @@ static void snow_coupling(column *c) {
   *H_abs = *H_abs + m_snow * latent_heat + *H_abs_snow;
   *H_abs_snow = -m_snow * latent_heat;
   *H = *H_abs / m;
-  getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 5701);
-  getT_aliased(c, *H, S_bu, T, phi, 5702);
+  getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 1);
+  getT_aliased(c, *H, S_bu, T, phi, 1);
   if (*T > 0.0 && *H_abs <= -*H_abs_snow) {
     *H_abs_snow = *H_abs_snow + *H_abs;
     *H_abs = 0.0;
-    getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 5701);
-    getT_aliased(c, *H, S_bu, T, phi, 5702);
+    getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 1);
+    getT_aliased(c, *H, S_bu, T, phi, 1);
   } else if (*T > 0.0 && *H_abs > -*H_abs_snow) {
     *H_abs = (*H_abs + *H_abs_snow) * m / m_snow / (1.0 + m / m_snow);
     *H_abs_snow = *H_abs * m_snow / m;
-    getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 5701);
-    getT_aliased(c, *H, S_bu, T, phi, 5702);
+    getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 1);
+    getT_aliased(c, *H, S_bu, T, phi, 1);
   } else {
     jj = 0;
     while (fabs(*T - *T_snow) > (double)0.1f && jj < 201) {
@@ -581,8 +582,8 @@ static void snow_coupling(column *c) {
       *H_abs = *H_abs + sg * c_s * m_snow;
       jj = jj + 1;
       *H = *H_abs / m;
-      getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 5701);
-      getT_aliased(c, *H, S_bu, T, phi, 5702);
+      getT_aliased(c, *H_abs_snow / m_snow, S_abs_snow / m_snow, T_snow, phi_s, 1);
+      getT_aliased(c, *H, S_bu, T, phi, 1);
     }
     if (jj > 200 && fabs(*T - *T_snow) > 1.0) STOP(16, 1);
   }
@@ -626,7 +627,7 @@ static void snow_thermo(column *c, int meltwater) {
   S_bu_snow = c->S_abs_snow / *m_snow;
   psi_s_old = *psi_s_snow;
   T_in = *T_snow;
-  getT(c, H_snow, S_bu_snow, T_in, T_snow, &phi_snow, 5700);
+  getT(c, H_snow, S_bu_snow, T_in, T_snow, &phi_snow, 0);      /* the snow: layer 0 (include/samsim.h, samsim_get_status) */
   *psi_s_snow = *m_snow * phi_snow / rho_s / *thick_snow;
   *psi_l_snow = *m_snow * (1.0 - phi_snow) / rho_l / *thick_snow;
   if (*psi_s_snow + *psi_l_snow > 1.0) {

@@ -233,6 +233,23 @@ __global__ void refresh_s_bu(double *lay, const int32_t *n_active, const int32_t
   }
 }
 
+// The health check at the end of a step clamps S_abs >= 0 over the active layers (mo_grotz.f90:812-818); the step kernel applies it
+// in the first sweep of the NEXT step.  samsim_get_state applies it to what it returns (and to the device copy, which the next first
+// sweep would clamp to the same values), so the state at a step boundary is the reference's and a checkpoint holds nothing that still
+// waits for the clamp.  Columns that stopped, and columns uploaded since the last step (COLF_RESTART), keep what they hold.
+__global__ void clamp_s_abs(double *lay, const int32_t *n_active, const int32_t *status, const int32_t *flags, size_t ncol, int N, size_t col0,
+                            size_t w) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= w) return;
+  const size_t c = col0 + i;
+  if (status[c] || (flags[c] & COLF_RESTART)) return;
+  const int na = n_active[c];
+  for (int k = 0; k < na; ++k) {
+    const size_t j = DEV_LAY_INDEX(SAMSIM_A_S_ABS, k, c, N, ncol);
+    if (lay[j] < 0.0) lay[j] = 0.0;
+  }
+}
+
 // The boundary keeps [array][layer][column] (samsim_state_soa); the device layout is DEV_LAY_INDEX.  A window of columns passes
 // through a staging buffer in the boundary's layout: scatter = staging -> device layout, gather = the reverse.
 template <bool GATHER>
@@ -581,6 +598,11 @@ int samsim_get_state(samsim_handle *h, samsim_state_soa *s, int64_t col0) {
   rc = check_soa(h, s, col0);
   if (rc) return rc;
   const size_t N = (size_t)s->nlayer, nc = (size_t)h->ncol, w = (size_t)s->ncol;
+  if (h->stepped) {
+    hipLaunchKernelGGL(clamp_s_abs, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, h->stream, h->lay, h->n_active, h->status, h->flags,
+                       nc, (int)N, (size_t)col0, w);
+    HIPCHK(hipGetLastError());
+  }
   if (s->narr == SAMSIM_NARR && h->stepped) {
     hipLaunchKernelGGL(refresh_s_bu, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, h->stream, h->lay, h->n_active, h->status,
                        nc, (int)N, (size_t)col0, w);

@@ -756,8 +756,9 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
   bal = bal + (double)Na * (c.frad * dt);
   if (thin_snow || CL(thick_snow) >= thick_min) bal = bal + c.fl_q_bottom * dt - CL(fl_Q_snow) * dt;
   else bal = bal + c.fl_q_bottom * dt - CL(fl_Q1) * dt;
-  if (rc) STOPC(rc, rc_layer);
+  // (the reference evaluates the heat fluxes, mo_grotz.f90:584, before the second getT sweep, :598: a column that fails both reports 431)
   if (fabs(bal / dt) > 0.00001) STOPC(431, 0);
+  if (rc) STOPC(rc, rc_layer);
 }
 
 }  // namespace

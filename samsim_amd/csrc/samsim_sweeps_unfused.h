@@ -42,6 +42,10 @@ __device__ RARE void sweep_thermo_expulsion(Col &c, const Ctx &x, bool all_phi, 
   bool regular = true;
   const double th_mid_rule = LAYU(SAMSIM_A_THICK, g.n_top + 1);
   const bool check_col = (c.flags & COLF_REGULAR) == 0 || (c.flags & (COLF_RESTART | COLF_REGRID)) != 0;
+  // A state that samsim_set_state has just uploaded has no previous step: its salt is taken as it is, as the reference takes its
+  // initial state (a negative S_abs then meets gravity drainage's MINVAL(S_abs) test, STOP 1337).  samsim_get_state returns the
+  // clamped values, so a checkpoint holds nothing this sweep would have clamped.
+  const bool uploaded = (c.flags & COLF_RESTART) != 0;
   const bool check_wave = wave_any(check_col);
   const int kmax = wave_max(Na);
   auto run = [&](auto check_tag) {
@@ -60,7 +64,7 @@ __device__ RARE void sweep_thermo_expulsion(Col &c, const Ctx &x, bool all_phi, 
       if (CHECK && k >= 2 && thick != thick_by_rule(k, g.n_top, g.n_middle, th_mid_rule, g.thick_0)) regular = false;
       double S_abs = cur.S;
       cur = nxt; nxt = nn;
-      if (S_abs < 0.0) {  // health check of the previous step, mo_grotz.f90:812-818 (element-wise clamp)
+      if (S_abs < 0.0 && !uploaded) {  // health check of the previous step, mo_grotz.f90:812-818 (element-wise clamp)
         S_abs = 0.0;
         LAYU(SAMSIM_A_S_ABS, k) = S_abs;
       }

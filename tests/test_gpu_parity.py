@@ -201,16 +201,21 @@ def test_failed_columns_are_frozen_and_reported():
     cfg, _ = tcs.testcase1(1)
     ncol = 8
     st = st1.replicate(ncol)
-    st.arr("S_abs")[3, 2] = -5.0e3      # strongly negative salt -> gravity-drainage / health-check STOP
-    st.arr("H_abs")[0, 5] = -1.0e15     # absurd enthalpy -> getT cannot converge (STOP 99)
-    st.arr("m")[10, 6] = -st.arr("m")[10, 6]  # negative mass -> negative solid fraction (STOP 1337)
+    # What the oracle does with each corruption (tests/stop_seeds.py has the seeds that do stop, site by site):
+    st.arr("S_abs")[3, 2] = -5.0e3      # strongly negative salt: NO stop -- S_bu < 0 sends getT down its fresh-ice branch, and the first
+    #                                     mass_transfer of the expelled brine clamps its transfer to -S_abs, which brings S_abs(4) to 0
+    #                                     before gravity drainage tests MINVAL(S_abs); the column runs on with a salt-free layer 4
+    st.arr("H_abs")[0, 5] = -1.0e15     # absurd enthalpy: getT of layer 1 cannot converge, STOP 99 in the first step, layer 1
+    st.arr("m")[10, 6] = -st.arr("m")[10, 6]  # negative mass: NO stop -- H = H_abs/m > 0 makes the layer liquid (phi = 0), so psi_s(11) is
+    #                                     -0.0, which MINVAL(psi_s) < 0 does not catch; the column runs on with its negative mass
     g, o = pair(cfg, ncol, st, clock)
     g.step(300)
     o.step(300)
     (sg, stepg, layg), (so, stepo, layo) = g.get_status(), o.get_status()
     assert np.array_equal(sg, so), (sg, so)
     assert np.array_equal(stepg, stepo), (stepg, stepo)
-    assert set(np.nonzero(so)[0]) >= {5}, so
+    assert np.array_equal(layg, layo), (layg, layo)
+    assert set(np.nonzero(so)[0]) == {5} and so[5] == 99 and stepo[5] == clock["step"] + 1 and layo[5] == 1, (so, stepo, layo)
     healthy = np.array([0, 1, 3, 4, 7])  # untouched columns next to the corrupted ones
     assert not so[healthy].any()
     a, b = g.get_state(), o.get_state()
