@@ -67,6 +67,13 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: z0, dz                                ! depth axis only, metres
   END TYPE samsim_profile_request
 
+  ! samsim_get_histogram / samsim_get_profile_histogram: the value bins, edges E_j = v0 + j*dv, j = 0..nvbins; a row of counts has nvbins + 2 entries
+  INTEGER, PARAMETER :: SAMSIM_HIST_MAX_VBINS = 254
+  TYPE, BIND(C) :: samsim_hist_bins
+     INTEGER(c_int32_t) :: struct_size, nvbins
+     REAL(c_double)     :: v0, dv
+  END TYPE samsim_hist_bins
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -219,6 +226,24 @@ MODULE mo_samsim_capi
        TYPE(samsim_profile_request), INTENT(in) :: rq
        INTEGER(c_int32_t), VALUE :: group
        TYPE(samsim_stat), INTENT(out) :: out(*)
+     END FUNCTION
+     !> fixed-edge histogram of a per-column scalar (slot 0-based, -1 = N_active); counts(nvbins+2), with by_group = 1 counts(nvbins+2, ngroups)
+     INTEGER(c_int) FUNCTION samsim_get_histogram(h, slot, vb, by_group, counts) BIND(C, name='samsim_get_histogram')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: slot
+       TYPE(samsim_hist_bins), INTENT(in) :: vb
+       INTEGER(c_int32_t), VALUE :: by_group
+       INTEGER(c_int64_t), INTENT(out) :: counts(*)
+     END FUNCTION
+     !> joint histogram over depth bin x value bin of one layer array (rq%narrays = 1); group -1 = every column; counts(nvbins+2, nbins)
+     INTEGER(c_int) FUNCTION samsim_get_profile_histogram(h, rq, vb, group, counts) BIND(C, name='samsim_get_profile_histogram')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(samsim_profile_request), INTENT(in) :: rq
+       TYPE(samsim_hist_bins), INTENT(in) :: vb
+       INTEGER(c_int32_t), VALUE :: group
+       INTEGER(c_int64_t), INTENT(out) :: counts(*)
      END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')

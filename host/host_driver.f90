@@ -5,7 +5,7 @@
 !!
 !! New surface the reference does not have (SURVEY.md, introduction): a namelist file `samsim.nml`
 !!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites,
-!!                 profile_bins, profile_dz, profile_origin, stats_by_site /
+!!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max /
 !! (col0 / ncol_total: this process owns the global columns col0 .. col0+ncol-1 of an ensemble of ncol_total -- one host
 !! process per GPU, contiguous column ranges, no exchange between them, SURVEY.md section 8e)
 !!   &samsim_flags <any flag of mo_data.f90:136-155 or scalar set by mo_init> /       (overrides init(testcase))
@@ -36,6 +36,8 @@ MODULE mo_data
   REAL(wp)            :: profile_dz = 0._wp  !< width of a depth bin [m]
   INTEGER             :: profile_origin = 0  !< 0 depth below the ice surface, 1 height above the ice bottom
   LOGICAL             :: stats_by_site = .FALSE.   !< with more than one site: the ensemble statistics per site as well (dat_ens_site.dat, dat_ens_profile_*_site<kk>.dat)
+  INTEGER             :: hist_bins = 0       !< > 0: histogram of the ice thickness over the ensemble in hist_bins bins at every output point (dat_ens_hist_thickness.dat)
+  REAL(wp)            :: hist_max = 0._wp    !< upper edge of the last bin [m]: edges j*hist_max/hist_bins, j = 0..hist_bins
   LOGICAL             :: by_site = .FALSE.   !< stats_by_site asked for and the run has more than one site: the handle carries the sites as group labels
   INTEGER             :: i_time, i_time_out
   REAL(wp)            :: fl_q_bottom = 0._wp, T_top = 0._wp, fl_sw = 0._wp, fl_rest = 0._wp, T2m = 0._wp, tank_depth = 0._wp
@@ -519,6 +521,43 @@ CONTAINS
     DEALLOCATE(q)
   END SUBROUTINE output_profile
 
+  !> dat_ens_hist_thickness.dat, and with statistics by site dat_ens_hist_thickness_site.dat: opened only when the run asks for the
+  !! histogram (hist_bins > 0)
+  SUBROUTINE output_begin_hist()
+    IF (hist_bins <= 0) RETURN
+    OPEN(56, file='./output/dat_ens_hist_thickness.dat', STATUS='replace', Recl=64 + 11*(hist_bins + 2))
+    IF (by_site) OPEN(57, file='./output/dat_ens_hist_thickness_site.dat', STATUS='replace', Recl=64 + 11*(hist_bins + 2))
+  END SUBROUTINE output_begin_hist
+
+  !> One row per output point: the time, then the hist_bins + 2 counts of the ice thickness over the ensemble (samsim_get_histogram:
+  !! below 0, the hist_bins bins of width hist_max/hist_bins, at or above hist_max).  With statistics by site one row per output point
+  !! and site as well -- time, 1-based site, counts --, all sites from one call.
+  SUBROUTINE output_hist(h, time)
+    TYPE(c_ptr), INTENT(in) :: h
+    REAL(wp),    INTENT(in) :: time
+    TYPE(samsim_hist_bins) :: vb
+    INTEGER(c_int64_t), ALLOCATABLE :: cnt(:, :)
+    CHARACTER(len=64) :: fmt
+    INTEGER :: s
+    IF (hist_bins <= 0) RETURN
+    vb%struct_size = INT(c_sizeof(vb), c_int32_t)
+    vb%nvbins = INT(hist_bins, c_int32_t)
+    vb%v0 = 0._wp; vb%dv = hist_max/REAL(hist_bins, wp)
+    ALLOCATE(cnt(hist_bins + 2, 1))
+    CALL samsim_check(samsim_get_histogram(h, INT(S_THICKNESS - 1, c_int32_t), vb, 0_c_int32_t, cnt), 'samsim_get_histogram')
+    WRITE(fmt, '(A,I0,A)') '(F14.1,', hist_bins + 2, 'I11)'
+    WRITE(56, fmt) time, cnt(:, 1)
+    DEALLOCATE(cnt)
+    IF (.NOT. by_site) RETURN
+    ALLOCATE(cnt(hist_bins + 2, nsites))
+    CALL samsim_check(samsim_get_histogram(h, INT(S_THICKNESS - 1, c_int32_t), vb, 1_c_int32_t, cnt), 'samsim_get_histogram')
+    WRITE(fmt, '(A,I0,A)') '(F14.1,I10,', hist_bins + 2, 'I11)'
+    DO s = 1, nsites
+       WRITE(57, fmt) time, s, cnt(:, s)
+    END DO
+    DEALLOCATE(cnt)
+  END SUBROUTINE output_hist
+
   !> the units of dat_ens_profile_{T,S_bu,psi_l}_site<kk>.dat: array a = 1..3 of site s = 1..nsites.  nsites is at most
   !! SIZE(sites) = 16 (the namelist holds no more directories), so the units stay within 601..648 and <kk> within two digits.
   INTEGER FUNCTION site_unit(a, s)
@@ -582,6 +621,10 @@ CONTAINS
 
   SUBROUTINE output_end()
     INTEGER :: u
+    IF (hist_bins > 0) THEN
+       CLOSE(56)
+       IF (by_site) CLOSE(57)
+    END IF
     IF (by_site) THEN
        CLOSE(55)
        IF (profile_bins > 0) THEN
@@ -775,6 +818,7 @@ CONTAINS
                fl_lw_input, T2m_input, precip_input, site_of_column, c_null_ptr, c_null_ptr), 'samsim_set_forcing_sites')
        END IF
     END IF
+    CALL output_begin_hist()
     st%ncol = ncol; st%nlayer = cfg%nlayer; st%narr = SAMSIM_NARR
     st%lay = c_loc(lay); st%scal = c_loc(scal); st%n_active = c_loc(n_active)
     IF (cfg%bgc_flag == 2) THEN
@@ -812,6 +856,7 @@ CONTAINS
           CALL output_ensemble(h, o%time)
           CALL output_profile(h, o%time)
           CALL output_site(h, o%time)
+          CALL output_hist(h, o%time)
           time = o%time
           thick1 = olay(1, 1, A_THICK)
           ! console progress line, mo_grotz.f90:371-381
@@ -858,7 +903,7 @@ PROGRAM SAMSIM
   CHARACTER*12000 :: description
   LOGICAL         :: have_nml
   NAMELIST /samsim_run/ testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, &
-       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site
+       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max
 
   testcase    = 1
   description = 'MI355X-native batched column solver'
@@ -870,6 +915,10 @@ PROGRAM SAMSIM
      READ(nml_unit, NML=samsim_run, IOSTAT=ios)
      IF (ios > 0) THEN
         PRINT *, 'error in namelist group samsim_run'
+        STOP 4
+     END IF
+     IF (hist_bins < 0 .OR. hist_bins > SAMSIM_HIST_MAX_VBINS .OR. (hist_bins > 0 .AND. .NOT. hist_max > 0._wp)) THEN
+        PRINT *, 'samsim_run: hist_bins must lie in 0 ..', SAMSIM_HIST_MAX_VBINS, ' and hist_max must be > 0'
         STOP 4
      END IF
   END IF

@@ -349,6 +349,50 @@ int samsim_set_groups(samsim_handle *h, int32_t ngroups, const int32_t *group_of
 int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, samsim_stat *out);
 int samsim_get_group_profile_stats(samsim_handle *h, const samsim_profile_request *rq, int32_t group, samsim_stat *out);
 
+/* Fixed-edge histograms of the ensemble, reduced on the device: how the columns are DISTRIBUTED, where the statistics above give
+ * four moments -- the ice-thickness distribution of a perturbed ensemble, the share of columns above a threshold, the median and
+ * the 5-95 % band of a profile (from the counts on the host: quantile brackets).  The two entry points below were added without a
+ * change of SAMSIM_ABI_VERSION (it stays 6): new symbols only, found by symbol as the group functions are.  The output has a fixed
+ * size and the counts are integers; this is not exact selection.
+ *
+ *   Edges.  E_j = v0 + j*dv, j = 0..nvbins (the product is rounded, then the sum; no fused multiply-add).
+ *   Entries.  A row of counts has nvbins + 2 entries.  The entry of a value v is idx(v) = the number of edges E_j, j = 0..nvbins,
+ *     with E_j <= v: entry 0 holds v < E_0, entry j+1 holds E_j <= v < E_{j+1}, entry nvbins+1 holds v >= E_nvbins.  A NaN compares
+ *     false with every edge and lands in entry 0.  The definition holds exactly, against the rounded edges, not to within a rounding:
+ *     the device may guess j from (v - v0)/dv, and then corrects the guess against the edges themselves.
+ *   samsim_get_histogram.  slot is an enum samsim_scalar or SAMSIM_STAT_N_ACTIVE (the value is then (double)n_active).
+ *     by_group == 0: counts[nvbins+2] over the columns with status == 0.  by_group == 1: counts[ngroups][nvbins+2]; group g covers the
+ *     columns with status == 0 and label g (samsim_set_groups), and all groups are reduced in one walk over the row.
+ *   samsim_get_profile_histogram.  rq is a request of samsim_get_profile_stats with narrays == 1; counts[rq->nbins][nvbins+2], a joint
+ *     histogram over depth bin x value bin.  The value of column c in bin b is exactly the v of samsim_get_profile_stats -- BY_LAYER
+ *     the layer value a_k, BY_DEPTH W_b / L_b from the same sums in the same order --, and a column contributes to bin b under exactly
+ *     the same condition (BY_LAYER: the layer exists; BY_DEPTH: L_b > 0).  group == -1: every column with status == 0, no labels
+ *     needed.  group >= 0: only the columns with that label, one group per call as with samsim_get_group_profile_stats.
+ *     A request is served in passes of `chunk` depth bins, each a walk over the layers of every column as in the profile statistics:
+ *     passes = ceil(nbins / chunk), chunk = 64 up to 121 value bins, falling to 42 at SAMSIM_HIST_MAX_VBINS (the walk's tile and
+ *     the count table share the 64 KiB of LDS of a workgroup: chunk = min(64, 65 024 / (520 + 4 * ((nvbins + 2) | 1)))).
+ *   Invariants.  The entries of a row sum to the `count` that the matching statistics call returns (samsim_get_ensemble_stats,
+ *     samsim_get_group_stats, samsim_get_profile_stats, samsim_get_group_profile_stats).  Integer counts, no floating-point
+ *     atomics: two calls on the same state return the same bytes.  Relabelling columns outside g leaves g's row unchanged.
+ *     Like every getter the calls wait for the handle's streams; they change neither the state, the clock nor the output snapshot.
+ *   Errors, all found before any device work.  SAMSIM_ERR_ARG: h, vb, rq or counts NULL.  SAMSIM_ERR_ABI: wrong struct_size of either
+ *     struct.  SAMSIM_ERR_ARG: nvbins out of range; a non-finite v0 or dv; dv <= 0; edges that are not all finite and strictly
+ *     increasing (checked on the host over all nvbins+1 edges); a bad slot; by_group other than 0 or 1; by_group == 1 without labels.
+ *     samsim_get_profile_histogram checks in this order: every check of samsim_get_profile_stats, in its order; narrays != 1; the
+ *     vb checks as above; group < -1, or group >= 0 without labels, or group >= ngroups.
+ *   Device scratch: at most SAMSIM_HIST_SCRATCH_BYTES whatever ncol and the request are (the 64-bit counts of one request);
+ *     allocated on first use, kept in the handle, freed by samsim_destroy.  Only counts come back to the host. */
+#define SAMSIM_HIST_MAX_VBINS 254          /* value bins; a row of counts has nvbins + 2 entries */
+#define SAMSIM_HIST_SCRATCH_BYTES (2ull << 20)   /* 1 024 rows (groups, or depth bins) of 256 int64 counts */
+typedef struct samsim_hist_bins {
+  int32_t struct_size;   /* = sizeof(samsim_hist_bins) */
+  int32_t nvbins;        /* 1..SAMSIM_HIST_MAX_VBINS   */
+  double  v0, dv;        /* edges E_j = v0 + j*dv, j = 0..nvbins */
+} samsim_hist_bins;
+int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins *vb, int32_t by_group, int64_t *counts);
+int samsim_get_profile_histogram(samsim_handle *h, const samsim_profile_request *rq, const samsim_hist_bins *vb,
+                                 int32_t group, int64_t *counts);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

@@ -66,6 +66,41 @@ class ProfileRequest(C.Structure):
                 ("narrays", C.c_int32), ("arrays", C.c_int32 * PROFILE_MAX_ARRAYS), ("z0", C.c_double), ("dz", C.c_double)]
 
 
+HIST_MAX_VBINS = 254        # SAMSIM_HIST_MAX_VBINS
+
+
+class HistBins(C.Structure):
+    """samsim_hist_bins: edges E_j = v0 + j*dv, j = 0..nvbins"""
+    _fields_ = [("struct_size", C.c_int32), ("nvbins", C.c_int32), ("v0", C.c_double), ("dv", C.c_double)]
+
+
+def hist_bins(nvbins, v0, dv) -> "HistBins":
+    return HistBins(C.sizeof(HistBins), int(nvbins), float(v0), float(dv))
+
+
+def hist_edges(nvbins, v0, dv) -> np.ndarray:
+    """the nvbins + 1 edges as the library forms them: the product is rounded, then the sum"""
+    return np.float64(v0) + np.arange(int(nvbins) + 1, dtype=np.float64) * np.float64(dv)
+
+
+def quantile_bracket(counts, v0, dv, q):
+    """(lo, hi) with the r-th smallest value of the data in [lo, hi), from one row of counts of Solver.histogram /
+    Solver.profile_histogram (nvbins + 2 entries): n = sum of the row, rank r = max(1, ceil(q n)), i = the first entry whose
+    cumulative count reaches r, lo = E_{i-1} and hi = E_i, with -inf and +inf for the two outer entries"""
+    counts = np.asarray(counts, dtype=np.int64)
+    if counts.ndim != 1 or counts.size < 3:
+        raise ValueError("one row of nvbins + 2 counts is needed")
+    n = int(counts.sum())
+    if n == 0:
+        raise ValueError("an empty row has no quantiles")
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("q outside [0, 1]")
+    r = max(1, int(np.ceil(q * n)))
+    i = int(np.searchsorted(np.cumsum(counts), r, side="left"))
+    e = hist_edges(counts.size - 2, v0, dv)
+    return (-np.inf if i == 0 else float(e[i - 1])), (np.inf if i == counts.size - 1 else float(e[i]))
+
+
 STAT_DTYPE = np.dtype([("count", np.int64), ("mean", np.float64), ("min", np.float64), ("max", np.float64), ("std", np.float64)])
 
 
@@ -243,6 +278,13 @@ class Solver:
                      "get_group_stats": [vp, C.c_int32, C.POINTER(C.c_int32), C.c_void_p],
                      "get_group_profile_stats": [vp, C.POINTER(ProfileRequest), C.c_int32, C.c_void_p]}
         for n, a in group_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # the histograms came the same way
+        hist_sig = {"get_histogram": [vp, C.c_int32, C.POINTER(HistBins), C.c_int32, C.c_void_p],
+                    "get_profile_histogram": [vp, C.POINTER(ProfileRequest), C.POINTER(HistBins), C.c_int32, C.c_void_p]}
+        for n, a in hist_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -455,6 +497,11 @@ class Solver:
         names = list(names)
         if axis == "depth" and (nbins is None or dz is None):
             raise ValueError("axis='depth' needs nbins and dz")
+        rq = self._profile_request(names, axis, origin, nbins, z0, dz)
+        out = self.profile_stats_raw(rq) if group is None else self.profile_stats_raw(rq, group)
+        return {n: out[i] for i, n in enumerate(names)}
+
+    def _profile_request(self, names, axis, origin, nbins, z0, dz) -> ProfileRequest:
         rq = ProfileRequest()
         rq.struct_size = C.sizeof(ProfileRequest)
         rq.axis, rq.origin = PROFILE_AXES[axis], PROFILE_ORIGINS[origin]
@@ -463,8 +510,39 @@ class Solver:
         for i, n in enumerate(names[:PROFILE_MAX_ARRAYS]):
             rq.arrays[i] = A[n]
         rq.z0, rq.dz = float(z0), float(0.0 if dz is None else dz)
-        out = self.profile_stats_raw(rq) if group is None else self.profile_stats_raw(rq, group)
-        return {n: out[i] for i, n in enumerate(names)}
+        return rq
+
+    def histogram_raw(self, slot, vb: HistBins, by_group=0) -> np.ndarray:
+        """samsim_get_histogram with the arguments as given (no checks on this side): int64 [nvbins+2], with by_group
+        [ngroups, nvbins+2]"""
+        w = max(0, min(vb.nvbins, HIST_MAX_VBINS)) + 2
+        rows = max(1, self.ngroups) if by_group == 1 else 1
+        buf = np.zeros((rows, w), dtype=np.int64)
+        self._chk(self._f("get_histogram")(self._h, int(slot), C.byref(vb), int(by_group), buf.ctypes.data), "get_histogram")
+        return buf if by_group == 1 else buf[0]
+
+    def histogram(self, name, nvbins, v0, dv, by_group=False) -> np.ndarray:
+        """fixed-edge histogram of a scalar from SCALARS or "N_active" over the columns without a STOP code
+        (samsim_get_histogram): edges v0 + j dv, j = 0..nvbins; entry 0 counts the values below the first edge, entry j+1 those
+        in [E_j, E_{j+1}), entry nvbins+1 those at or above the last edge.  int64 [nvbins+2]; by_group: [ngroups, nvbins+2] per
+        group of set_groups"""
+        return self.histogram_raw(-1 if name == "N_active" else S[name], hist_bins(nvbins, v0, dv), 1 if by_group else 0)
+
+    def profile_histogram_raw(self, rq: ProfileRequest, vb: HistBins, group=-1) -> np.ndarray:
+        """samsim_get_profile_histogram with the arguments as given (no checks on this side): int64 [nbins, nvbins+2]"""
+        buf = np.zeros((max(1, min(rq.nbins, PROFILE_MAX_BINS)), max(0, min(vb.nvbins, HIST_MAX_VBINS)) + 2), dtype=np.int64)
+        self._chk(self._f("get_profile_histogram")(self._h, C.byref(rq), C.byref(vb), int(group), buf.ctypes.data),
+                  "get_profile_histogram")
+        return buf
+
+    def profile_histogram(self, name, nvbins, v0, dv, axis="layer", origin="top", nbins=None, z0=0.0, dz=None, group=None) -> np.ndarray:
+        """joint histogram over depth bin x value bin of one array from ARRAYS (samsim_get_profile_histogram): the bins and the
+        per-column bin values of profile_stats, the value entries of histogram.  int64 [nbins, nvbins+2]; group: only the
+        columns with that label of set_groups"""
+        if axis == "depth" and (nbins is None or dz is None):
+            raise ValueError("axis='depth' needs nbins and dz")
+        rq = self._profile_request([name], axis, origin, nbins, z0, dz)
+        return self.profile_histogram_raw(rq, hist_bins(nvbins, v0, dv), -1 if group is None else int(group))
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

@@ -16,6 +16,7 @@
 
 #include "samsim_device.h"
 #include "samsim_groups.h"
+#include "samsim_hist.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
 // samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS) over every column
@@ -69,6 +70,7 @@ struct samsim_handle {
   int32_t *groups = nullptr;   // [ncol] group label of each column (samsim_set_groups), owned by the caller as the forcing is
   int32_t ngroups = 0;         // 0: no labels
   void *d_group = nullptr;     // samsim_get_group_stats: the waves' partials of one slot, then its results (kGroupScratch bytes)
+  void *d_hist = nullptr;      // samsim_get_histogram / samsim_get_profile_histogram: the 64-bit counts of one request (kHistScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -208,6 +210,12 @@ constexpr size_t kGroupScratch = kGroupPartBytes + sizeof(samsim_stat) * SAMSIM_
 static_assert(kGroupScratch <= SAMSIM_GROUP_SCRATCH_BYTES, "group scratch bound of samsim.h");
 static_assert(DEV_GROUP_PART_ENTRIES >= SAMSIM_MAX_GROUPS, "at least one wave at the largest number of groups");
 static_assert(sizeof(GroupPartial) * SAMSIM_MAX_GROUPS <= (64u << 10), "a wave's table of every group fits the LDS of a workgroup");
+
+// device scratch of the histograms: the counts of the largest request, [ngroups][nvbins + 2] or [nbins][nvbins + 2]
+constexpr size_t kHistScratch = sizeof(int64_t) * (SAMSIM_HIST_MAX_VBINS + 2) *
+                                (SAMSIM_MAX_GROUPS > SAMSIM_PROFILE_MAX_BINS ? SAMSIM_MAX_GROUPS : SAMSIM_PROFILE_MAX_BINS);
+static_assert(kHistScratch <= SAMSIM_HIST_SCRATCH_BYTES && SAMSIM_HIST_SCRATCH_BYTES <= (16ull << 20), "histogram scratch bound of samsim.h");
+static_assert(sizeof(uint32_t) * DEV_HIST_LDS_COUNTS <= DEV_HIST_LDS_BYTES, "a wave's table of the scalar histogram fits the LDS of a workgroup");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -469,7 +477,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->lay); (void)hipFree(h->scal); (void)hipFree(h->n_active); (void)hipFree(h->status);
   (void)hipFree(h->err_layer); (void)hipFree(h->err_step); (void)hipFree(h->work);
   (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
-  (void)hipFree(h->groups); (void)hipFree(h->d_group);
+  (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
   (void)hipFree(h->ocean_dflq); (void)hipFree(h->ocean_sbu);
@@ -895,10 +903,8 @@ int samsim_get_ensemble_stats(samsim_handle *h, int32_t nslots, const int32_t *s
   return SAMSIM_OK;
 }
 
-// samsim_get_profile_stats over every column (labels null) or over the columns with label `group` (samsim_get_group_profile_stats)
-static int profile_stats(samsim_handle *h, const samsim_profile_request *rq, bool grouped, int32_t group, samsim_stat *out) {
-  // every check of the request first: nothing below touches the device before the request is known to be good
-  if (!h || !rq || !out) return SAMSIM_ERR_ARG;
+// the checks of a profile request, in the order samsim.h gives (h and rq are not null)
+static int check_profile_request(const samsim_handle *h, const samsim_profile_request *rq) {
   if (rq->struct_size != (int32_t)sizeof(samsim_profile_request)) return SAMSIM_ERR_ABI;
   const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
   if (!depth && rq->axis != SAMSIM_PROFILE_BY_LAYER) return SAMSIM_ERR_ARG;
@@ -908,8 +914,18 @@ static int profile_stats(samsim_handle *h, const samsim_profile_request *rq, boo
   for (int i = 0; i < rq->narrays; ++i)
     if (rq->arrays[i] < 0 || rq->arrays[i] >= SAMSIM_NARR) return SAMSIM_ERR_ARG;
   if (depth && (!std::isfinite(rq->z0) || !std::isfinite(rq->dz) || rq->z0 < 0.0 || !(rq->dz > 0.0))) return SAMSIM_ERR_ARG;
+  return SAMSIM_OK;
+}
+
+// samsim_get_profile_stats over every column (labels null) or over the columns with label `group` (samsim_get_group_profile_stats)
+static int profile_stats(samsim_handle *h, const samsim_profile_request *rq, bool grouped, int32_t group, samsim_stat *out) {
+  // every check of the request first: nothing below touches the device before the request is known to be good
+  if (!h || !rq || !out) return SAMSIM_ERR_ARG;
+  int rc = check_profile_request(h, rq);
+  if (rc) return rc;
+  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
   if (grouped && (!h->groups || group < 0 || group >= h->ngroups)) return SAMSIM_ERR_ARG;
-  int rc = use(h);
+  rc = use(h);
   if (rc) return rc;
   if (!h->d_prof) HIPCHK(hipMalloc(&h->d_prof, kProfScratch));
   ProfPartial *d_part = (ProfPartial *)h->d_prof;
@@ -979,6 +995,76 @@ int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slot
     HIPCHK(samsim_launch_group_stats(row, h->n_active, h->status, h->groups, h->ncol, h->ngroups, d_part, d_out, h->stream));
     HIPCHK(hipMemcpyAsync(out + (size_t)i * ng, d_out, sizeof(samsim_stat) * ng, hipMemcpyDeviceToHost, h->stream));
   }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+// the checks of the value bins of a histogram request, in the order samsim.h gives (vb is not null); fills the device's view
+static int check_hist_bins(const samsim_hist_bins *vb, HistEdges *e) {
+  if (vb->struct_size != (int32_t)sizeof(samsim_hist_bins)) return SAMSIM_ERR_ABI;
+  if (vb->nvbins < 1 || vb->nvbins > SAMSIM_HIST_MAX_VBINS) return SAMSIM_ERR_ARG;
+  if (!std::isfinite(vb->v0) || !std::isfinite(vb->dv)) return SAMSIM_ERR_ARG;
+  if (!(vb->dv > 0.0)) return SAMSIM_ERR_ARG;
+  double prev = 0.0;
+  for (int j = 0; j <= vb->nvbins; ++j) {   // E_j = v0 + j*dv as the device forms it: product rounded, then the sum
+    const double p = (double)j * vb->dv;
+    const double ej = vb->v0 + p;
+    if (!std::isfinite(ej) || (j > 0 && !(ej > prev))) return SAMSIM_ERR_ARG;
+    prev = ej;
+  }
+  e->v0 = vb->v0; e->dv = vb->dv; e->rdv = 1.0 / vb->dv; e->nvbins = vb->nvbins;
+  return SAMSIM_OK;
+}
+
+int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins *vb, int32_t by_group, int64_t *counts) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !vb || !counts) return SAMSIM_ERR_ARG;
+  HistEdges e;
+  int rc = check_hist_bins(vb, &e);
+  if (rc) return rc;
+  if (slot != SAMSIM_STAT_N_ACTIVE && (slot < 0 || slot >= SAMSIM_NSCAL)) return SAMSIM_ERR_ARG;
+  if (by_group != 0 && by_group != 1) return SAMSIM_ERR_ARG;
+  if (by_group && !h->groups) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  if (!h->d_hist) HIPCHK(hipMalloc(&h->d_hist, kHistScratch));
+  const int ng = by_group ? h->ngroups : 1;
+  const size_t bytes = sizeof(int64_t) * (size_t)ng * (size_t)(e.nvbins + 2);
+  const double *row = (slot == SAMSIM_STAT_N_ACTIVE) ? nullptr : h->scal + (size_t)slot * (size_t)h->ncol;
+  HIPCHK(hipMemsetAsync(h->d_hist, 0, bytes, h->stream));
+  HIPCHK(samsim_launch_hist(row, h->n_active, h->status, by_group ? h->groups : nullptr, h->ncol, ng, e,
+                            (unsigned long long *)h->d_hist, h->stream));
+  HIPCHK(hipMemcpyAsync(counts, h->d_hist, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_get_profile_histogram(samsim_handle *h, const samsim_profile_request *rq, const samsim_hist_bins *vb, int32_t group,
+                                 int64_t *counts) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !rq || !vb || !counts) return SAMSIM_ERR_ARG;
+  int rc = check_profile_request(h, rq);
+  if (rc) return rc;
+  if (rq->narrays != 1) return SAMSIM_ERR_ARG;
+  HistEdges e;
+  rc = check_hist_bins(vb, &e);
+  if (rc) return rc;
+  if (group < -1 || (group >= 0 && (!h->groups || group >= h->ngroups))) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  if (!h->d_hist) HIPCHK(hipMalloc(&h->d_hist, kHistScratch));
+  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
+  const size_t bytes = sizeof(int64_t) * (size_t)rq->nbins * (size_t)(e.nvbins + 2);
+  const int chunk = dev_hist_chunk(e.nvbins);
+  HIPCHK(hipMemsetAsync(h->d_hist, 0, bytes, h->stream));
+  // one pass per chunk of depth bins, all on the handle's stream; the passes add into disjoint rows of the counts
+  for (int b0 = 0; b0 < rq->nbins; b0 += chunk) {
+    const int nb = rq->nbins - b0 < chunk ? rq->nbins - b0 : chunk;
+    HIPCHK(samsim_launch_profile_hist(h->lay, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol, h->cfg.nlayer,
+                                      rq->axis, rq->origin, rq->arrays[0], b0, nb, rq->nbins, depth ? rq->z0 : 0.0, depth ? rq->dz : 1.0, e,
+                                      (unsigned long long *)h->d_hist, h->stream));
+  }
+  HIPCHK(hipMemcpyAsync(counts, h->d_hist, bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }

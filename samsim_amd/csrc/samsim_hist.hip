@@ -1,0 +1,180 @@
+// samsim_hist.hip -- device-side fixed-edge histograms of the ensemble (samsim_get_histogram, samsim_get_profile_histogram,
+// include/samsim.h): of a per-column scalar over all columns or per group, and of the layer profiles as a joint histogram over
+// depth bin x value bin.
+//
+// Scalars: one wave owns one 64-column block at a time (lane = column) and strides over the blocks with a fixed grid, as
+// group_stats_kernel does; its loads of the row, of status and of the labels are coalesced and the next block's are under way while
+// this block is counted.  Profiles: the block walk of the profile statistics (samsim_profile_walk.h) fills the LDS tile [bin][lane];
+// then lane j walks row j of the tile and increments its own row of the count table -- no atomics in the loop.  Either way a wave
+// counts in 32-bit LDS entries and adds its table to the 64-bit result with integer atomics at the end (samsim_hist.h); there is no
+// floating-point atomic and no floating-point sum at all, so two calls return the same bytes.
+#include <hip/hip_runtime.h>
+
+#include "samsim_hist.h"
+#include "samsim_profile_walk.h"
+
+namespace {
+
+using namespace profile_walk;
+
+// The entry of a value: the number of edges E_j = v0 + j*dv, j = 0..nvbins, with E_j <= v.  The quotient only guesses j; the guess
+// is then moved until E_j <= v < E_{j+1} holds for the rounded edges themselves (the host has checked that they increase strictly).
+// A NaN compares false and lands in entry 0.
+__device__ __forceinline__ int hist_entry(double v, const HistEdges &e) {
+  if (!(v >= e.v0)) return 0;   // below E_0 = v0 + 0*dv = v0, or NaN
+  const double t = (v - e.v0) * e.rdv;
+  int j = t >= (double)e.nvbins ? e.nvbins : (t > 0.0 ? (int)t : 0);   // the largest j with E_j <= v, if the guess is right
+  while (j < e.nvbins && e.v0 + (double)(j + 1) * e.dv <= v) ++j;
+  while (j > 0 && e.v0 + (double)j * e.dv > v) --j;
+  return j + 1;
+}
+
+// what a wave counted, added to the 64-bit result
+__device__ __forceinline__ void flush_table(const uint32_t *table, int n, int lane, unsigned long long *out) {
+  for (int i = lane; i < n; i += 64) {
+    const uint32_t c = table[i];
+    if (c) atomicAdd(out + i, (unsigned long long)c);
+  }
+}
+
+// the lane's column of block blk: its group (-1: stopped, unlabelled or beyond ncol; without labels 0) and its value
+__device__ __forceinline__ void load_column(const double *row, const int32_t *n_active, const int32_t *status, const int32_t *labels,
+                                            long long ncol, int ngroups, long long blk, int lane, int &lab, double &v) {
+  const long long col = blk * 64 + lane;
+  lab = -1; v = 0.0;
+  if (col < ncol) {
+    const int l = labels ? labels[col] : 0;
+    lab = (status[col] == 0 && l < ngroups) ? l : -1;
+    v = row ? row[col] : (double)n_active[col];
+  }
+}
+
+// LDS: the wave's table [ngroups][W] of 32-bit counts in LDS (dev_hist_in_lds); else every lane adds into the result itself
+template <bool LDS>
+__global__ void __launch_bounds__(64) hist_kernel(const double *__restrict__ row, const int32_t *__restrict__ n_active,
+                                                  const int32_t *__restrict__ status, const int32_t *__restrict__ labels, long long ncol,
+                                                  int ngroups, HistEdges e, unsigned long long *__restrict__ counts) {
+  extern __shared__ uint32_t table[];   // [ngroups][W]
+  const int lane = threadIdx.x, W = e.nvbins + 2;
+  if (LDS) {
+    for (int i = lane; i < ngroups * W; i += 64) table[i] = 0;
+    __syncthreads();
+  }
+  const long long nblk = (ncol + 63) / 64;
+  int lab, lab_next = -1;
+  double v, v_next = 0.0;
+  load_column(row, n_active, status, labels, ncol, ngroups, blockIdx.x, lane, lab, v);
+  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    // the next block's loads are under way while this block is counted
+    if (blk + gridDim.x < nblk) load_column(row, n_active, status, labels, ncol, ngroups, blk + gridDim.x, lane, lab_next, v_next);
+    if (lab >= 0) {
+      const int i = lab * W + hist_entry(v, e);
+      if (LDS) atomicAdd(table + i, 1u);
+      else atomicAdd(counts + i, 1ull);
+    }
+    lab = lab_next; v = v_next;
+  }
+  if (LDS) {
+    __syncthreads();
+    flush_table(table, ngroups * W, lane, counts);
+  }
+}
+
+// Lane j counts row j of the tile: the values of bin j of the columns whose bit j is set in their lane's mask.
+__device__ __forceinline__ void count_tile(const double *tile, unsigned long long *smask, unsigned long long mask, int lane, int nb,
+                                           const HistEdges &e, uint32_t *my_row) {
+  smask[lane] = mask;
+  __syncthreads();
+  if (lane < nb) {
+    const double *row = tile + lane * kTileStride;
+    for (int i = 0; i < 64; ++i)
+      if ((smask[i] >> lane) & 1ull) my_row[hist_entry(row[i], e)] += 1;
+  }
+  __syncthreads();
+}
+
+// LDS of the two profile kernels: tile [chunk][kTileStride] doubles, the lanes' masks, the count table [chunk][stride] (samsim_hist.h)
+struct ProfLds {
+  double *tile;
+  unsigned long long *smask;
+  uint32_t *table;
+};
+__device__ __forceinline__ ProfLds carve(unsigned char *lds, int chunk, int stride, int lane) {
+  ProfLds p;
+  p.tile = (double *)lds;
+  p.smask = (unsigned long long *)(p.tile + (size_t)chunk * kTileStride);
+  p.table = (uint32_t *)(p.smask + 64);
+  for (int i = lane; i < chunk * stride; i += 64) p.table[i] = 0;
+  __syncthreads();
+  return p;
+}
+// the wave's rows of the table added to rows b0 .. b0+nb-1 of the result [nbins][W]
+__device__ __forceinline__ void flush_rows(const uint32_t *table, int stride, int nb, int W, int lane, unsigned long long *out) {
+  __syncthreads();
+  for (int r = 0; r < nb; ++r) flush_table(table + r * stride, W, lane, out + (size_t)r * W);
+}
+
+__global__ void __launch_bounds__(64) hist_layer_kernel(const double *__restrict__ lay, const int32_t *__restrict__ n_active,
+                                                        const int32_t *__restrict__ status, const int32_t *__restrict__ labels, int group,
+                                                        long long ncol, int N, int origin, int array, int b0, int nb, int chunk,
+                                                        HistEdges e, unsigned long long *__restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int lane = threadIdx.x, stride = (e.nvbins + 2) | 1;
+  const ProfLds p = carve(lds, chunk, stride, lane);
+  const long long nblk = (ncol + 63) / 64;
+  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
+    TileSink sink{p.tile, lane, 0};
+    layer_block(lay, ncol, N, blk, lane, na, origin, array, b0, nb, sink);
+    count_tile(p.tile, p.smask, sink.mask, lane, nb, e, p.table + lane * stride);
+  }
+  flush_rows(p.table, stride, nb, e.nvbins + 2, lane, counts + (size_t)b0 * (e.nvbins + 2));
+}
+
+__global__ void __launch_bounds__(64) hist_depth_kernel(const double *__restrict__ lay, const int32_t *__restrict__ n_active,
+                                                        const int32_t *__restrict__ status, const int32_t *__restrict__ labels, int group,
+                                                        long long ncol, int N, int origin, int array, int b0, int nb, int chunk, int lead,
+                                                        double z0, double dz, HistEdges e, unsigned long long *__restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int lane = threadIdx.x, stride = (e.nvbins + 2) | 1;
+  const ProfLds p = carve(lds, chunk, stride, lane);
+  const long long nblk = (ncol + 63) / 64;
+  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
+    TileSink sink{p.tile, lane, 0};
+    depth_block(lay, ncol, N, blk, lane, na, origin, array, b0, nb, lead, z0, dz, sink);
+    count_tile(p.tile, p.smask, sink.mask, lane, nb, e, p.table + lane * stride);
+  }
+  flush_rows(p.table, stride, nb, e.nvbins + 2, lane, counts + (size_t)b0 * (e.nvbins + 2));
+}
+
+}  // namespace
+
+extern "C" hipError_t samsim_launch_hist(const double *row, const int32_t *n_active, const int32_t *status, const int32_t *labels,
+                                         long long ncol, int ngroups, HistEdges e, unsigned long long *counts, hipStream_t stream) {
+  const long long nblk = (ncol + 63) / 64;
+  const int grid = (int)(nblk < DEV_HIST_GRID ? nblk : DEV_HIST_GRID);
+  if (dev_hist_in_lds(ngroups, e.nvbins))
+    hipLaunchKernelGGL(hist_kernel<true>, dim3(grid), dim3(64), sizeof(uint32_t) * (size_t)ngroups * (e.nvbins + 2), stream, row, n_active,
+                       status, labels, ncol, ngroups, e, counts);
+  else
+    hipLaunchKernelGGL(hist_kernel<false>, dim3(grid), dim3(64), 0, stream, row, n_active, status, labels, ncol, ngroups, e, counts);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t samsim_launch_profile_hist(const double *lay, const int32_t *n_active, const int32_t *status, const int32_t *labels,
+                                                 int group, long long ncol, int N, int axis, int origin, int array, int b0, int nb, int nbins,
+                                                 double z0, double dz, HistEdges e, unsigned long long *counts, hipStream_t stream) {
+  const long long nblk = (ncol + 63) / 64;
+  const int grid = (int)(nblk < DEV_HIST_GRID ? nblk : DEV_HIST_GRID);
+  const int chunk = dev_hist_chunk(e.nvbins);
+  const size_t lds = dev_hist_profile_lds(e.nvbins);
+  if (nb > chunk || lds > DEV_HIST_LDS_BYTES) return hipErrorInvalidValue;
+  if (axis == SAMSIM_PROFILE_BY_LAYER)
+    hipLaunchKernelGGL(hist_layer_kernel, dim3(grid), dim3(64), lds, stream, lay, n_active, status, labels, group, ncol, N, origin, array, b0,
+                       nb, chunk, e, counts);
+  else
+    hipLaunchKernelGGL(hist_depth_kernel, dim3(grid), dim3(64), lds, stream, lay, n_active, status, labels, group, ncol, N, origin, array, b0,
+                       nb, chunk, origin == SAMSIM_PROFILE_FROM_TOP ? b0 > 0 : b0 + nb < nbins, z0, dz, e, counts);
+  return hipGetLastError();
+}

@@ -1,0 +1,179 @@
+// samsim_profile_walk.h -- how one wave walks the layers of one 64-column block and finds every column's value in every bin of a
+// profile request (include/samsim.h, samsim_get_profile_stats): shared by the statistics (samsim_profile.hip) and the joint
+// histograms (samsim_hist.hip), which differ only in what they do with the finished values.  The step kernel does not include
+// this header.
+//
+// A walk serves one requested array and the bins [b0, b0 + nb) of the request, nb <= 64, for one block (lane = column).  It reads
+// 512-byte rows from the device layout [block][layer][array][64]; only the rows the request needs are touched (the array itself --
+// S_abs and m for S_bu -- and thick for the depth axis), and the rows of kAhead layers are requested before the first is waited
+// for.  Every lane moves through the bins of its own column monotonically and hands each finished bin value to the sink:
+//   sink.put(r, v)   -- the lane's column has the value v in bin b0 + r, 0 <= r < nb; at most once per (lane, r) and block.
+#ifndef SAMSIM_PROFILE_WALK_H
+#define SAMSIM_PROFILE_WALK_H
+
+#include <hip/hip_runtime.h>
+
+#include "samsim_device.h"
+
+namespace profile_walk {
+
+constexpr int kAhead = 8;                        // layers whose rows a wave requests before it waits for the first
+constexpr size_t kRow = DEV_ROWB / sizeof(double);   // doubles from one layer row of a 64-column block to the next (samsim_device.h)
+constexpr int kTileStride = DEV_PROF_BINS + 1;   // row stride of the LDS tile in doubles: lane j reads row j without a bank pile-up
+
+// The sink both reductions use: an LDS tile [bin][lane] of the block's values and, per lane, the mask of the bins its column
+// reached.  After the block lane j walks row j of the tile (a transposition through LDS).
+struct TileSink {
+  double *tile;
+  int lane;
+  unsigned long long mask;
+  __device__ __forceinline__ void put(int r, double v) {
+    tile[r * kTileStride + lane] = v;
+    mask |= 1ull << r;
+  }
+};
+
+__device__ __forceinline__ int wave_max(int v) {
+  for (int w = 32; w > 0; w >>= 1) { const int o = __shfl_xor(v, w); v = o > v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+  for (int w = 32; w > 0; w >>= 1) { const int o = __shfl_xor(v, w); v = o < v ? o : v; }
+  return v;
+}
+
+__device__ __forceinline__ double ld(const double *p) { return __builtin_nontemporal_load(p); }
+
+// The value of the requested array in one layer row (`row` = the lane's element of array 0 of that layer) in two halves, so that a
+// wave can request the rows of several layers before it waits for the first: row_request loads the stored value -- for the bulk
+// salinity S_abs and m --, row_value forms a_k from them: S_abs / m where m is not zero (what samsim_get_state returns after a
+// step), the stored S_bu in the rare lane with m = 0.
+__device__ __forceinline__ void row_request(const double *row, int array, double &x, double &y) {
+  const bool sbu = array == SAMSIM_A_S_BU;
+  x = ld(row + (sbu ? (int)SAMSIM_A_S_ABS : array) * 64);
+  y = sbu ? ld(row + SAMSIM_A_M * 64) : 1.0;
+}
+__device__ __forceinline__ double row_value(const double *row, int array, double x, double y) {
+  if (array != SAMSIM_A_S_BU) return x;
+  if (y != 0.0) return x / y;
+  return ld(row + SAMSIM_A_S_BU * 64);
+}
+
+// the lane's column of block blk: its number of active layers, 0 for a column that stopped, lies beyond ncol or -- with a label row
+// (samsim_get_group_profile_stats) -- carries another label than `group`: such a column behaves like a stopped one
+__device__ __forceinline__ int active_layers(const int32_t *n_active, const int32_t *status, const int32_t *labels, int group, long long ncol,
+                                             long long blk, int lane, int N) {
+  const long long col = blk * 64 + lane;
+  if (col >= ncol || status[col] != 0) return 0;
+  if (labels && labels[col] != group) return 0;
+  const int na = n_active[col];
+  return na < 0 ? 0 : (na > N ? N : na);
+}
+
+// ---- layer axis: bin b holds layer b+1 (from the top) or layer N_active-b (from the bottom); bins [b0, b0+nb) of block blk,
+// na = active_layers() of the lane's column
+template <class Sink>
+__device__ __forceinline__ void layer_block(const double *__restrict__ lay, long long ncol, int N, long long blk, int lane, int na, int origin,
+                                            int array, int b0, int nb, Sink &sink) {
+  const int kmax = wave_max(na);
+  const double *base = lay + DEV_LAY_INDEX(0, 0, blk * 64 + lane, N, ncol);   // the lane's element of array 0, layer 1
+  int klo, khi;
+  if (origin == SAMSIM_PROFILE_FROM_TOP) {
+    klo = b0 + 1;
+    khi = b0 + nb < kmax ? b0 + nb : kmax;
+  } else {
+    const int kmin = wave_min(na > 0 ? na : N + 1);   // fewest active layers among the columns that count
+    klo = kmin - b0 - nb + 1;
+    klo = klo < 1 ? 1 : klo;
+    khi = kmax - b0;
+  }
+  for (int k0 = klo; k0 <= khi; k0 += kAhead) {   // the rows of kAhead layers requested together
+    double x[kAhead], y[kAhead];
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u) {
+      x[u] = y[u] = 0.0;
+      if (k0 + u <= khi) row_request(base + (size_t)(k0 + u - 1) * kRow, array, x[u], y[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u) {
+      const int k = k0 + u;
+      const int r = origin == SAMSIM_PROFILE_FROM_TOP ? k - 1 - b0 : na - k - b0;
+      if (k <= khi && k <= na && r >= 0 && r < nb) sink.put(r, row_value(base + (size_t)(k - 1) * kRow, array, x[u], y[u]));
+    }
+  }
+}
+
+// ---- depth axis: bin b is [z0 + b dz, z0 + (b+1) dz) below the ice surface (from the top) or above the ice bottom; a column's
+// value in a bin is the overlap-weighted mean of its layers there (samsim.h); bins [b0, b0+nb) of block blk.  lead: the chunk does
+// not begin where the walk begins (from the top: b0 > 0; from the bottom: not the last chunk).
+template <class Sink>
+__device__ __forceinline__ void depth_block(const double *__restrict__ lay, long long ncol, int N, long long blk, int lane, int na, int origin,
+                                            int array, int b0, int nb, int lead, double z0, double dz, Sink &sink) {
+  const bool top = origin == SAMSIM_PROFILE_FROM_TOP;
+  const int kmax = wave_max(na);
+  const double *base = lay + DEV_LAY_INDEX(0, 0, blk * 64 + lane, N, ncol);   // the lane's element of array 0, layer 1
+  double H = 0.0;
+  if (!top) {   // the ice thickness first: Z_k = Z_{k-1} + thick(k), k ascending
+#pragma unroll 4
+    for (int k = 1; k <= kmax; ++k) {
+      const double t = ld(base + (size_t)(k - 1) * kRow + SAMSIM_A_THICK * 64);
+      H = k <= na ? H + t : H;
+    }
+  }
+  int cur = top ? b0 : b0 + nb - 1;   // the bin the lane's column is filling
+  const int step = top ? 1 : -1;
+  double Z = 0.0, W = 0.0, L = 0.0;
+  for (int k0 = 1; k0 <= kmax; k0 += kAhead) {   // the rows of kAhead layers requested together, then the lanes' bin walks
+    // the rows only while some column of the wave still has bins of this chunk to fill
+    if (!__any(k0 <= na && cur >= b0 && cur < b0 + nb)) break;
+    double tk[kAhead], x[kAhead], y[kAhead];
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u) {
+      tk[u] = 0.0;
+      if (k0 + u <= kmax) tk[u] = ld(base + (size_t)(k0 + u - 1) * kRow + SAMSIM_A_THICK * 64);
+    }
+    if (lead) {
+      // A chunk that does not begin where the walk begins: while no column of the wave has reached the chunk the layers overlap
+      // none of its bins, so only Z moves on -- by the same additions -- and the array rows are not requested.
+      double Ze = Z;
+#pragma unroll
+      for (int u = 0; u < kAhead; ++u) Ze = k0 + u <= na ? Ze + tk[u] : Ze;
+      const bool reached = top ? Ze > z0 + (double)b0 * dz : H - Ze < z0 + (double)(b0 + nb) * dz;
+      if (!__any(reached && k0 <= na)) {
+        Z = Ze;
+        continue;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u) {
+      x[u] = y[u] = 0.0;
+      if (k0 + u <= kmax) row_request(base + (size_t)(k0 + u - 1) * kRow, array, x[u], y[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < kAhead; ++u) {
+      const int k = k0 + u;
+      if (k <= na) {
+        const double a = row_value(base + (size_t)(k - 1) * kRow, array, x[u], y[u]);
+        const double Zn = Z + tk[u];
+        const double lo = top ? Z : H - Zn, hi = top ? Zn : H - Z;
+        while (cur >= b0 && cur < b0 + nb) {
+          const double e0 = z0 + (double)cur * dz, e1 = z0 + (double)(cur + 1) * dz;
+          const double xo = (hi < e1 ? hi : e1) - (lo > e0 ? lo : e0);
+          const double o = xo > 0.0 ? xo : 0.0;
+          L += o;
+          W += o * a;
+          if (!(top ? hi > e1 : lo < e0)) break;   // the layer ends inside this bin
+          if (L > 0.0) sink.put(cur - b0, W / L);
+          W = 0.0; L = 0.0;
+          cur += step;
+        }
+        Z = Zn;
+      }
+    }
+  }
+  if (cur >= b0 && cur < b0 + nb && L > 0.0) sink.put(cur - b0, W / L);   // the bin in which the column ends
+}
+
+}  // namespace profile_walk
+
+#endif
