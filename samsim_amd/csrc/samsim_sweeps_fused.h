@@ -463,7 +463,8 @@ __device__ __forceinline__ void sweep_down_fused(Col &c, const Ctx &x, bool stor
   // T_top, fl_Q(1) and fl_Q_snow; the freezing point of layer 1 (S_abs(1), m(1) stay as they are unless wet snow adds slush);
   // the snow's enthalpy after the heat fluxes, hence whether the second snow_thermo of the step can find it wet.  The rows are
   // skipped only when none of the conditions can hold, so a late reader never meets a column without them (refill_psi_rows is
-  // the safety net; tools/melt_ensemble_status.py drives 4 096 columns through a melt season and freeze-up and counts its calls).
+  // the safety net; tests/test_gpu_melt_onset.py runs a wave of columns through their melt onsets, and with the counter build
+  // asserts that no lane calls it).
   if (decide_psi && Na >= 3) {
     surface_flux<K>(c, x);
     surface_done = true;
@@ -472,7 +473,8 @@ __device__ __forceinline__ void sweep_down_fused(Col &c, const Ctx &x, bool stor
     bool snow_wet = false;
     if (CL(thick_snow) > 0.0) {
       // snow_thermo finds liquid water iff H_abs_snow / m_snow > -latent_heat (getT's fresh branch); the up sweep adds
-      // (fl_Q(1) - fl_Q_snow)*dt to a snow cover thicker than thick_min (thinner ones take the unfused path: never here)
+      // (fl_Q(1) - fl_Q_snow)*dt to a snow cover thicker than thick_min.  A thinner one does come here (its coupling runs inside
+      // this sweep) and exchanges heat with layer 1 as well: it counts as wet whatever its enthalpy
       const double H_new = CL(H_abs_snow) + (CL(fl_Q1) - CL(fl_Q_snow)) * dt;
       snow_wet = !(CL(thick_snow) >= thick_min) || !(H_new / CL(m_snow) <= -latent_heat);
     }

@@ -468,8 +468,9 @@ __device__ RARE void down_unfused(Col &c, const Ctx &x, long long col, double ti
 
 // Safety net of the stored-row decision (sweep_down_fused): a late reader of psi_s / psi_l / psi_g -- func_freeboard, flush3 -- in a
 // step whose down sweep skipped the rows of layers >= 3.  The sweep evaluates those readers' conditions exactly before it skips
-// (profiles/r3_melt_ensemble_status.json: a free-running ensemble through melt season and freeze-up never gets here; the stamps
-// build counts the calls, CT_REFILL), so this is not on any tested trajectory; should a column ever arrive, it keeps running:
+// (tests/test_gpu_melt_onset.py: a wave of columns 2..17 steps before their melt onsets, and crafted leaders of single conditions,
+// never get here; the stamps build counts the calls, CT_REFILL, and that test asserts the count is 0), so this is not on any
+// tested trajectory; should a column ever arrive, it keeps running:
 // the rows are filled by one Expulsion pass over the finished layers (temperature of the second sweep, current masses) -- the
 // values the next step's first sweep will form -- instead of the column being stopped.
 template <class K>
