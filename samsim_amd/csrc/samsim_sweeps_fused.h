@@ -151,18 +151,63 @@ __device__ __forceinline__ void prologue_top_layer(Col &c, const Ctx &x) {
 }
 
 // Beer-law absorption alone (no gravity drainage this step): fl_rad(N_active), mo_heat_fluxes.f90:151-155
+// temp2(k) = temp2(k-1) * exp(-extinc * thick(k)) from temp2(0) = beer0, and fl_rad(N_active) = temp2(Na-1) - temp2(Na): a chain of Na
+// sequentially rounded products, so the order is the reference's and nothing is re-associated or raised to a power.  What varies is
+// how the factor is found.  A column that follows the grid rule is walked as the fused sweeps walk it -- layer 1, top block, elastic
+// block, bottom block -- with the factor formed where a stretch begins (exp is a function of its operand alone: the bits are those of
+// a loop that forms it per layer, whichever layer that is) and the multiply alone inside: per layer one instruction where the
+// per-layer form spends a thickness select, a `thick != th_prev` test with its exec-mask region around the inlined exp, a
+// `k == Na` test with its region and the multiply.  A hand-made column keeps the per-layer form.
 template <class K>
 __device__ RARE void sweep_beer(Col &c, const Ctx &x, double beer0) {
   const samsim_config &g = x.p->cfg;
-  const int Na = c.Na;
-  double temp2 = beer0, e = 0.0, th_prev = -1.0;
-  const bool regular = (c.flags & COLF_REGULAR) != 0;
-  const double th_mid = LAYU(SAMSIM_A_THICK, g.n_top + 1);
-  for (int k = 1; k <= Na; ++k) {
-    const double thick = (regular && k >= 2) ? thick_by_rule(k, g.n_top, g.n_middle, th_mid, g.thick_0) : LAYU(SAMSIM_A_THICK, k);
-    if (thick != th_prev) { e = exp(-extinc * thick); th_prev = thick; }
-    if (k == Na) c.frad = temp2 - temp2 * e;
-    temp2 = temp2 * e;
+  const int Na = c.Na;   // (>= 1: samsim_set_state, and no regrid removes the last layer)
+  // Polar night: no lane of the wave has short-wave radiation to absorb.  With temp2 = beer0 = +-0 and a factor e in [0, 1] (thick is
+  // a positive number) every product temp2 * e is a zero of temp2's sign, and fl_rad = temp2 - temp2 * e is x - x of two equal zeros,
+  // which rounds to +0.0 whatever their sign: the value set here.  (A NaN beer0 compares unequal and takes the walk.)  This assumes
+  // finite positive thicknesses, as every valid state has: a NaN thick, or one below -355 m whose factor overflows, made the loop's
+  // fl_rad a NaN (0 * NaN, 0 * inf) where this gives +0.0 -- in a column that is already lost.
+  if (!wave_any(beer0 != 0.0)) { c.frad = 0.0; return; }
+  if ((c.flags & COLF_REGULAR) != 0) {
+    // the layer count as a scalar where the lanes (those of the wave that are here) agree on it, else the wave's maximum with each
+    // lane's value kept at its own N_active; a lane's products past its bottom layer are not read
+    const int n0 = __builtin_amdgcn_readfirstlane(Na);
+    const bool same = !wave_any(Na != n0);
+    const int kend = same ? n0 : wave_max(Na);
+    const int b0 = g.n_top, b1 = g.n_top + g.n_middle;
+    double temp2 = beer0, frad = 0.0;
+    // (one copy of the stretch in the listing, and so of the inlined exp, walked four times: the pass is inlined at three places of
+    // every step kernel, and the top and bottom blocks forming the same factor twice costs a column some forty instructions)
+#pragma unroll 1
+    for (int st = 0; st < 4; ++st) {
+      const int klo = st == 0 ? 1 : (st == 1 ? 2 : (st == 2 ? b0 + 1 : b1 + 1));
+      const int khi_s = st == 0 ? 1 : (st == 1 ? b0 : (st == 2 ? b1 : kend));
+      if (klo > kend) break;
+      if (klo > khi_s) continue;
+      const int khi = khi_s < kend ? khi_s : kend;
+      const double thick = st == 0 ? LAYU(SAMSIM_A_THICK, 1) : (st == 2 ? LAYU(SAMSIM_A_THICK, g.n_top + 1) : g.thick_0);
+      const double e = exp(-extinc * thick);
+      if (same) {
+        const int kmul = khi < kend ? khi : kend - 1;    // (the product of layer N_active itself is only fl_rad's subtrahend)
+        for (int k = klo; k <= kmul; ++k) temp2 = temp2 * e;
+        if (khi == kend) frad = temp2 - temp2 * e;
+      } else {
+        for (int k = klo; k <= khi; ++k) {
+          const double t = temp2 * e;
+          if (k == Na) frad = temp2 - t;
+          temp2 = t;
+        }
+      }
+    }
+    c.frad = frad;
+  } else {
+    double temp2 = beer0, e = 0.0, th_prev = -1.0;
+    for (int k = 1; k <= Na; ++k) {
+      const double thick = LAYU(SAMSIM_A_THICK, k);
+      if (thick != th_prev) { e = exp(-extinc * thick); th_prev = thick; }
+      if (k == Na) c.frad = temp2 - temp2 * e;
+      temp2 = temp2 * e;
+    }
   }
 }
 
