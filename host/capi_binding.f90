@@ -74,6 +74,13 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: v0, dv
   END TYPE samsim_hist_bins
 
+  ! samsim_get_covariance / samsim_get_profile_regression: joint population moments of a predictor x and a value y
+  INTEGER, PARAMETER :: SAMSIM_SENS_MAX_SLOTS = 8
+  TYPE, BIND(C) :: samsim_pair_stat
+     INTEGER(c_int64_t) :: count
+     REAL(c_double)     :: mean_x, mean_y, var_x, var_y, cov
+  END TYPE samsim_pair_stat
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -244,6 +251,26 @@ MODULE mo_samsim_capi
        TYPE(samsim_hist_bins), INTENT(in) :: vb
        INTEGER(c_int32_t), VALUE :: group
        INTEGER(c_int64_t), INTENT(out) :: counts(*)
+     END FUNCTION
+     !> count, means and population covariance matrix of up to SAMSIM_SENS_MAX_SLOTS per-column scalars (slots 0-based, -1 = N_active)
+     !! over the columns with status 0 (group -1) or with that 0-based label as well; mean(nslots), cov(nslots, nslots) (symmetric)
+     INTEGER(c_int) FUNCTION samsim_get_covariance(h, nslots, slots, group, count, mean, cov) BIND(C, name='samsim_get_covariance')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: nslots
+       INTEGER(c_int32_t), INTENT(in) :: slots(*)
+       INTEGER(c_int32_t), VALUE :: group
+       INTEGER(c_int64_t), INTENT(out) :: count
+       REAL(c_double), INTENT(out) :: mean(*), cov(*)
+     END FUNCTION
+     !> per bin of a profile request the joint moments of the bin value and the scalar predictor_slot (0-based, -1 = N_active);
+     !! group -1 = every column; out(nbins, narrays), bin fastest
+     INTEGER(c_int) FUNCTION samsim_get_profile_regression(h, rq, predictor_slot, group, out) BIND(C, name='samsim_get_profile_regression')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(samsim_profile_request), INTENT(in) :: rq
+       INTEGER(c_int32_t), VALUE :: predictor_slot, group
+       TYPE(samsim_pair_stat), INTENT(out) :: out(*)
      END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')

@@ -5,7 +5,7 @@
 !!
 !! New surface the reference does not have (SURVEY.md, introduction): a namelist file `samsim.nml`
 !!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites,
-!!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max /
+!!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens /
 !! (col0 / ncol_total: this process owns the global columns col0 .. col0+ncol-1 of an ensemble of ncol_total -- one host
 !! process per GPU, contiguous column ranges, no exchange between them, SURVEY.md section 8e)
 !!   &samsim_flags <any flag of mo_data.f90:136-155 or scalar set by mo_init> /       (overrides init(testcase))
@@ -38,6 +38,7 @@ MODULE mo_data
   LOGICAL             :: stats_by_site = .FALSE.   !< with more than one site: the ensemble statistics per site as well (dat_ens_site.dat, dat_ens_profile_*_site<kk>.dat)
   INTEGER             :: hist_bins = 0       !< > 0: histogram of the ice thickness over the ensemble in hist_bins bins at every output point (dat_ens_hist_thickness.dat)
   REAL(wp)            :: hist_max = 0._wp    !< upper edge of the last bin [m]: edges j*hist_max/hist_bins, j = 0..hist_bins
+  LOGICAL             :: sens = .FALSE.      !< sensitivities to the perturbation at every output point: slopes and correlations on dT2m and precip_scale (dat_ens_sens.dat, dat_ens_sens_profile_*.dat)
   LOGICAL             :: by_site = .FALSE.   !< stats_by_site asked for and the run has more than one site: the handle carries the sites as group labels
   INTEGER             :: i_time, i_time_out
   REAL(wp)            :: fl_q_bottom = 0._wp, T_top = 0._wp, fl_sw = 0._wp, fl_rest = 0._wp, T2m = 0._wp, tank_depth = 0._wp
@@ -558,6 +559,64 @@ CONTAINS
     DEALLOCATE(cnt)
   END SUBROUTINE output_hist
 
+  !> dat_ens_sens.dat and, with profile_bins > 0, dat_ens_sens_profile_{T,S_bu,psi_l}.dat: opened only when the run asks for the
+  !! sensitivities (sens)
+  SUBROUTINE output_begin_sens()
+    INTEGER :: recl
+    IF (.NOT. sens) RETURN
+    OPEN(58, file='./output/dat_ens_sens.dat', STATUS='replace', Recl=12288)
+    IF (profile_bins <= 0) RETURN
+    recl = 64 + 42*profile_bins
+    OPEN(59, file='./output/dat_ens_sens_profile_T.dat',     STATUS='replace', Recl=recl)
+    OPEN(60, file='./output/dat_ens_sens_profile_S_bu.dat',  STATUS='replace', Recl=recl)
+    OPEN(61, file='./output/dat_ens_sens_profile_psi_l.dat', STATUS='replace', Recl=recl)
+  END SUBROUTINE output_begin_sens
+
+  !> a / b, 0 where b is not positive (a variance of 0: no slope, no correlation)
+  PURE FUNCTION ratio(a, b) RESULT(r)
+    REAL(wp), INTENT(in) :: a, b
+    REAL(wp) :: r
+    r = 0._wp
+    IF (b > 0._wp) r = a/b
+  END FUNCTION ratio
+
+  !> One row per output point in dat_ens_sens.dat: the time, then for each of the six scalars of dat_ensemble.dat the count, the
+  !! regression slope on dT2m, the slope on precip_scale and the two correlations, from one covariance matrix of the six and the two
+  !! perturbations (samsim_get_covariance).  With profile_bins > 0 one row per output point in each profile file: the time, then per
+  !! depth bin the count, the slope of the bin value on precip_scale and their correlation (samsim_get_profile_regression).
+  SUBROUTINE output_sens(h, time)
+    TYPE(c_ptr), INTENT(in) :: h
+    REAL(wp),    INTENT(in) :: time
+    INTEGER(c_int32_t) :: slots(8)
+    INTEGER(c_int64_t) :: cnt
+    REAL(c_double) :: mean(8), cov(8, 8)
+    TYPE(samsim_profile_request) :: rq
+    TYPE(samsim_pair_stat), ALLOCATABLE :: q(:, :)
+    CHARACTER(len=64) :: fmt
+    INTEGER :: a, b, j
+    IF (.NOT. sens) RETURN
+    slots = (/ S_THICKNESS - 1, S_THICK_SNOW - 1, S_BULK_SALIN - 1, S_FREEBOARD - 1, S_T_TOP - 1, -1, S_DT2M - 1, S_PRECIP_SCALE - 1 /)
+    CALL samsim_check(samsim_get_covariance(h, 8_c_int32_t, slots, -1_c_int32_t, cnt, mean, cov), 'samsim_get_covariance')
+    WRITE(58, '(F14.1,6(I10,4ES16.8))') time, (cnt, ratio(cov(j, 7), cov(7, 7)), ratio(cov(j, 8), cov(8, 8)), &
+         ratio(cov(j, 7), SQRT(cov(j, j)*cov(7, 7))), ratio(cov(j, 8), SQRT(cov(j, j)*cov(8, 8))), j = 1, 6)
+    IF (profile_bins <= 0) RETURN
+    rq%struct_size = INT(c_sizeof(rq), c_int32_t)
+    rq%axis = SAMSIM_PROFILE_BY_DEPTH; rq%origin = INT(profile_origin, c_int32_t)
+    rq%nbins = INT(profile_bins, c_int32_t); rq%narrays = 3
+    rq%arrays = 0
+    rq%arrays(1:3) = (/ A_T - 1, A_S_BU - 1, A_PSI_L - 1 /)
+    rq%z0 = 0._wp; rq%dz = profile_dz
+    ALLOCATE(q(profile_bins, 3))
+    CALL samsim_check(samsim_get_profile_regression(h, rq, INT(S_PRECIP_SCALE - 1, c_int32_t), -1_c_int32_t, q), &
+         'samsim_get_profile_regression')
+    WRITE(fmt, '(A,I0,A)') '(F14.1,', profile_bins, '(I10,2ES16.8))'
+    DO a = 1, 3
+       WRITE(58 + a, fmt) time, (q(b, a)%count, ratio(q(b, a)%cov, q(b, a)%var_x), &
+            ratio(q(b, a)%cov, SQRT(q(b, a)%var_x*q(b, a)%var_y)), b = 1, profile_bins)
+    END DO
+    DEALLOCATE(q)
+  END SUBROUTINE output_sens
+
   !> the units of dat_ens_profile_{T,S_bu,psi_l}_site<kk>.dat: array a = 1..3 of site s = 1..nsites.  nsites is at most
   !! SIZE(sites) = 16 (the namelist holds no more directories), so the units stay within 601..648 and <kk> within two digits.
   INTEGER FUNCTION site_unit(a, s)
@@ -621,6 +680,12 @@ CONTAINS
 
   SUBROUTINE output_end()
     INTEGER :: u
+    IF (sens) THEN
+       CLOSE(58)
+       IF (profile_bins > 0) THEN
+          CLOSE(59); CLOSE(60); CLOSE(61)
+       END IF
+    END IF
     IF (hist_bins > 0) THEN
        CLOSE(56)
        IF (by_site) CLOSE(57)
@@ -819,6 +884,7 @@ CONTAINS
        END IF
     END IF
     CALL output_begin_hist()
+    CALL output_begin_sens()
     st%ncol = ncol; st%nlayer = cfg%nlayer; st%narr = SAMSIM_NARR
     st%lay = c_loc(lay); st%scal = c_loc(scal); st%n_active = c_loc(n_active)
     IF (cfg%bgc_flag == 2) THEN
@@ -857,6 +923,7 @@ CONTAINS
           CALL output_profile(h, o%time)
           CALL output_site(h, o%time)
           CALL output_hist(h, o%time)
+          CALL output_sens(h, o%time)
           time = o%time
           thick1 = olay(1, 1, A_THICK)
           ! console progress line, mo_grotz.f90:371-381
@@ -903,7 +970,7 @@ PROGRAM SAMSIM
   CHARACTER*12000 :: description
   LOGICAL         :: have_nml
   NAMELIST /samsim_run/ testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, &
-       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max
+       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens
 
   testcase    = 1
   description = 'MI355X-native batched column solver'

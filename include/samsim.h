@@ -393,6 +393,55 @@ int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins 
 int samsim_get_profile_histogram(samsim_handle *h, const samsim_profile_request *rq, const samsim_hist_bins *vb,
                                  int32_t group, int64_t *counts);
 
+/* Ensemble sensitivities, reduced on the device: how two quantities of the same column vary TOGETHER over the ensemble, where
+ * everything above gives marginal results -- the covariance matrix of up to SAMSIM_SENS_MAX_SLOTS per-column scalars, and per depth
+ * bin the joint second moments of a layer profile and one per-column predictor, from which the host forms regression slopes
+ * (cov / var_x) and correlations (cov / sqrt(var_x var_y)): the response of the ice to the perturbation of samsim_set_forcing.  The
+ * two entry points below were added without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only, found by symbol as the
+ * group and histogram functions are.
+ *
+ *   Columns (both).  A column counts if its status is 0 and, with group >= 0, its label (samsim_set_groups) equals group.
+ *     group == -1: every column with status 0, no labels needed.  One group per call, as with samsim_get_group_profile_stats.
+ *   Slots (both).  A slot is an enum samsim_scalar or SAMSIM_STAT_N_ACTIVE (the value is then (double)n_active).  A slot may appear
+ *     twice in slots.  The perturbation slots SAMSIM_S_DT2M and SAMSIM_S_PRECIP_SCALE are the intended predictors.
+ *   samsim_get_covariance.  count = the number of columns that count; mean[i] = the mean of slot i over them; cov[i][j] = the
+ *     population covariance sum (x_i - mean_i)(x_j - mean_j) / count of slots i and j over them, the diagonal the variance.  One
+ *     triangle is computed and mirrored: cov[i][j] and cov[j][i] are the same bytes.  With count == 0 every output is 0.0.
+ *   samsim_get_profile_regression.  rq is a request of samsim_get_profile_stats with any narrays; out[narrays][nbins].  y is exactly
+ *     the v of that function for (array, bin), and a column contributes to a bin under exactly that function's condition (BY_LAYER:
+ *     the layer exists; BY_DEPTH: L_b > 0); x is the column's value of predictor_slot.  Per (array, bin), over the contributing
+ *     columns: count, mean_x, mean_y, var_x, var_y and cov, population moments (sums of products of deviations / count).  The set of
+ *     contributing columns differs from bin to bin, so mean_x and var_x are per-bin results.  With count == 0 the five doubles are
+ *     0.0.  Slope and correlation are not part of the ABI: the host forms them.  A request is served in passes of one array and at
+ *     most 64 bins, as samsim_get_profile_stats is.
+ *   Arithmetic.  Everything is formed from deviations -- Welford's update of means and co-moments per lane, Chan's pairwise
+ *     combination of (n, mean, co-moment) triples across lanes and waves --, never from sum xy - n mean_x mean_y.  No floating-point
+ *     atomics, a grid fixed by ncol alone, a fixed order of combination: two calls on the same state return the same bytes, and
+ *     relabelling columns outside `group` leaves the result unchanged, byte for byte.  Columns that hold identical values give means
+ *     equal to the value and variances and covariances of 0.0, exactly.  A slot listed twice gives identical rows and columns:
+ *     cov[i][j] == cov[i][i] == cov[j][j] bitwise.  samsim_get_profile_regression folds y with the fold and merge of the profile
+ *     statistics: count and mean_y are the count and mean bytes of samsim_get_profile_stats for the same request
+ *     (samsim_get_group_profile_stats with a group), and sqrt(var_y) is its std bytes.
+ *   Errors, all found before any device work, in this order.  samsim_get_covariance: SAMSIM_ERR_ARG for h, slots, count, mean or cov
+ *     NULL; nslots outside 1..SAMSIM_SENS_MAX_SLOTS; a bad slot; group < -1, group >= 0 without labels, or group >= ngroups.
+ *     samsim_get_profile_regression: SAMSIM_ERR_ARG for h, rq or out NULL; every check of samsim_get_profile_stats, in its order; a bad
+ *     predictor_slot; the group checks as above.
+ *   Like every getter the calls wait for the handle's streams; they change neither the state, the clock, the output snapshot nor the
+ *     labels.  Device scratch: at most SAMSIM_SENS_SCRATCH_BYTES whatever ncol and the request are (the waves' partials of one pass,
+ *     then the results); allocated on first use, kept in the handle, freed by samsim_destroy.  Only results come back to the host;
+ *     nothing is merged there.  A host that holds several handles or ranks can combine their results itself: (count, mean, count *
+ *     cov) are (n, mean, co-moment) triples, merged by the same Chan update. */
+#define SAMSIM_SENS_MAX_SLOTS 8
+#define SAMSIM_SENS_SCRATCH_BYTES (4ull << 20)
+typedef struct samsim_pair_stat {      /* 48 bytes */
+  int64_t count;
+  double  mean_x, mean_y, var_x, var_y, cov;   /* population moments: sums of products of deviations / count */
+} samsim_pair_stat;
+int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group,
+                          int64_t *count, double *mean /*[nslots]*/, double *cov /*[nslots][nslots]*/);
+int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request *rq, int32_t predictor_slot,
+                                  int32_t group, samsim_pair_stat *out /*[narrays][nbins]*/);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

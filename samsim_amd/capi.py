@@ -101,6 +101,43 @@ def quantile_bracket(counts, v0, dv, q):
     return (-np.inf if i == 0 else float(e[i - 1])), (np.inf if i == counts.size - 1 else float(e[i]))
 
 
+SENS_MAX_SLOTS = 8          # SAMSIM_SENS_MAX_SLOTS
+
+
+class PairStat(C.Structure):
+    """samsim_pair_stat: joint population moments of a predictor x and a bin value y over the contributing columns"""
+    _fields_ = [("count", C.c_int64), ("mean_x", C.c_double), ("mean_y", C.c_double), ("var_x", C.c_double), ("var_y", C.c_double),
+                ("cov", C.c_double)]
+
+
+PAIR_STAT_DTYPE = np.dtype([("count", np.int64), ("mean_x", np.float64), ("mean_y", np.float64), ("var_x", np.float64),
+                            ("var_y", np.float64), ("cov", np.float64)])
+
+
+def correlation(cov) -> np.ndarray:
+    """the correlation matrix of a covariance matrix (Solver.covariance): cov[i][j] / sqrt(cov[i][i] cov[j][j]), 0.0 where a
+    variance is 0"""
+    cov = np.asarray(cov, dtype=np.float64)
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1]:
+        raise ValueError("a square covariance matrix is needed")
+    var = np.diag(cov)
+    scale = np.sqrt(var[:, None] * var[None, :])
+    ok = scale > 0.0
+    return np.where(ok, cov / np.where(ok, scale, 1.0), 0.0)
+
+
+def slope_and_correlation(pair_stats):
+    """(slope, correlation) of y on x from an array of PAIR_STAT_DTYPE (Solver.profile_regression): cov / var_x and
+    cov / sqrt(var_x var_y), each 0.0 where a variance it divides by is 0"""
+    q = np.asarray(pair_stats)
+    vx, vy, c = q["var_x"], q["var_y"], q["cov"]
+    okx = vx > 0.0
+    slope = np.where(okx, c / np.where(okx, vx, 1.0), 0.0)
+    scale = np.sqrt(vx * vy)
+    ok = scale > 0.0
+    return slope, np.where(ok, c / np.where(ok, scale, 1.0), 0.0)
+
+
 STAT_DTYPE = np.dtype([("count", np.int64), ("mean", np.float64), ("min", np.float64), ("max", np.float64), ("std", np.float64)])
 
 
@@ -285,6 +322,13 @@ class Solver:
         hist_sig = {"get_histogram": [vp, C.c_int32, C.POINTER(HistBins), C.c_int32, C.c_void_p],
                     "get_profile_histogram": [vp, C.POINTER(ProfileRequest), C.POINTER(HistBins), C.c_int32, C.c_void_p]}
         for n, a in hist_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the sensitivities
+        sens_sig = {"get_covariance": [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p],
+                    "get_profile_regression": [vp, C.POINTER(ProfileRequest), C.c_int32, C.c_int32, C.c_void_p]}
+        for n, a in sens_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -543,6 +587,43 @@ class Solver:
             raise ValueError("axis='depth' needs nbins and dz")
         rq = self._profile_request([name], axis, origin, nbins, z0, dz)
         return self.profile_histogram_raw(rq, hist_bins(nvbins, v0, dv), -1 if group is None else int(group))
+
+    def covariance_raw(self, slots, group=-1):
+        """samsim_get_covariance with the arguments as given (no checks on this side): (count, mean [nslots], cov [nslots, nslots])"""
+        slots = [int(x) for x in slots]
+        n = len(slots)
+        arr = (C.c_int32 * max(1, n))(*slots)
+        count = C.c_int64(0)
+        m = max(1, min(n, SENS_MAX_SLOTS))
+        mean, cov = np.zeros(m), np.zeros((m, m))
+        self._chk(self._f("get_covariance")(self._h, n, arr, int(group), C.byref(count), mean.ctypes.data, cov.ctypes.data), "get_covariance")
+        return int(count.value), mean, cov
+
+    def covariance(self, names, group=None):
+        """(count, mean [n], cov [n, n]) of the scalars `names` (from SCALARS, or "N_active") over the columns without a STOP code --
+        with group: over those with that label of set_groups -- (samsim_get_covariance): population covariances, the diagonal the
+        variances; capi.correlation(cov) gives the correlations"""
+        return self.covariance_raw([-1 if n == "N_active" else S[n] for n in names], -1 if group is None else int(group))
+
+    def profile_regression_raw(self, rq: ProfileRequest, predictor_slot, group=-1) -> np.ndarray:
+        """samsim_get_profile_regression with the arguments as given (no checks on this side): PAIR_STAT_DTYPE [narrays][nbins]"""
+        out = np.zeros((max(0, min(rq.narrays, PROFILE_MAX_ARRAYS)), max(0, min(rq.nbins, PROFILE_MAX_BINS))), dtype=PAIR_STAT_DTYPE)
+        buf = np.zeros(max(1, out.size), dtype=PAIR_STAT_DTYPE)
+        self._chk(self._f("get_profile_regression")(self._h, C.byref(rq), int(predictor_slot), int(group), buf.ctypes.data),
+                  "get_profile_regression")
+        out.ravel()[:] = buf[:out.size]
+        return out
+
+    def profile_regression(self, names, predictor, axis="layer", origin="top", nbins=None, z0=0.0, dz=None, group=None):
+        """{name: PAIR_STAT_DTYPE array [nbins]}: per bin of profile_stats the joint moments of the bin value y of the array and the
+        column's scalar `predictor` x (from SCALARS, or "N_active") over the columns that contribute to the bin
+        (samsim_get_profile_regression); capi.slope_and_correlation gives dy/dx and the correlation per bin"""
+        names = list(names)
+        if axis == "depth" and (nbins is None or dz is None):
+            raise ValueError("axis='depth' needs nbins and dz")
+        rq = self._profile_request(names, axis, origin, nbins, z0, dz)
+        out = self.profile_regression_raw(rq, -1 if predictor == "N_active" else S[predictor], -1 if group is None else int(group))
+        return {n: out[i] for i, n in enumerate(names)}
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

@@ -17,6 +17,7 @@
 #include "samsim_device.h"
 #include "samsim_groups.h"
 #include "samsim_hist.h"
+#include "samsim_sens.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
 // samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS) over every column
@@ -71,6 +72,7 @@ struct samsim_handle {
   int32_t ngroups = 0;         // 0: no labels
   void *d_group = nullptr;     // samsim_get_group_stats: the waves' partials of one slot, then its results (kGroupScratch bytes)
   void *d_hist = nullptr;      // samsim_get_histogram / samsim_get_profile_histogram: the 64-bit counts of one request (kHistScratch bytes)
+  void *d_sens = nullptr;      // samsim_get_covariance / samsim_get_profile_regression: the waves' partials of one pass, then the results (kSensScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -216,6 +218,11 @@ constexpr size_t kHistScratch = sizeof(int64_t) * (SAMSIM_HIST_MAX_VBINS + 2) *
                                 (SAMSIM_MAX_GROUPS > SAMSIM_PROFILE_MAX_BINS ? SAMSIM_MAX_GROUPS : SAMSIM_PROFILE_MAX_BINS);
 static_assert(kHistScratch <= SAMSIM_HIST_SCRATCH_BYTES && SAMSIM_HIST_SCRATCH_BYTES <= (16ull << 20), "histogram scratch bound of samsim.h");
 static_assert(sizeof(uint32_t) * DEV_HIST_LDS_COUNTS <= DEV_HIST_LDS_BYTES, "a wave's table of the scalar histogram fits the LDS of a workgroup");
+
+// device scratch of the sensitivities: the partials of one pass (every pass reuses them), then the results of the largest request
+constexpr size_t kSensScratch = DEV_SENS_PART_BYTES + DEV_SENS_RESULT_BYTES;
+static_assert(kSensScratch <= SAMSIM_SENS_SCRATCH_BYTES && SAMSIM_SENS_SCRATCH_BYTES <= (16ull << 20), "sensitivity scratch bound of samsim.h");
+static_assert(sizeof(samsim_pair_stat) == 48, "samsim_pair_stat of samsim.h");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -477,7 +484,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->lay); (void)hipFree(h->scal); (void)hipFree(h->n_active); (void)hipFree(h->status);
   (void)hipFree(h->err_layer); (void)hipFree(h->err_step); (void)hipFree(h->work);
   (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
-  (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist);
+  (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
   (void)hipFree(h->ocean_dflq); (void)hipFree(h->ocean_sbu);
@@ -1065,6 +1072,65 @@ int samsim_get_profile_histogram(samsim_handle *h, const samsim_profile_request 
                                       (unsigned long long *)h->d_hist, h->stream));
   }
   HIPCHK(hipMemcpyAsync(counts, h->d_hist, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+// a slot of the statistics: an enum samsim_scalar, or SAMSIM_STAT_N_ACTIVE
+static bool good_slot(int32_t slot) { return slot == SAMSIM_STAT_N_ACTIVE || (slot >= 0 && slot < SAMSIM_NSCAL); }
+// one group per call: -1 every column, else a label of samsim_set_groups
+static bool good_group(const samsim_handle *h, int32_t group) { return group == -1 || (group >= 0 && h->groups && group < h->ngroups); }
+
+int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group, int64_t *count, double *mean, double *cov) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !slots || !count || !mean || !cov) return SAMSIM_ERR_ARG;
+  if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < nslots; ++i)
+    if (!good_slot(slots[i])) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  if (!h->d_sens) HIPCHK(hipMalloc(&h->d_sens, kSensScratch));
+  double *d_part = (double *)h->d_sens;
+  CovResult *d_out = (CovResult *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
+  SensRows rows{};
+  for (int i = 0; i < nslots; ++i) rows.row[i] = slots[i] == SAMSIM_STAT_N_ACTIVE ? nullptr : h->scal + (size_t)slots[i] * (size_t)h->ncol;
+  HIPCHK(samsim_launch_covariance(rows, nslots, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol, d_part, d_out,
+                                  h->stream));
+  CovResult res;
+  HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(CovResult), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *count = res.count;
+  std::memcpy(mean, res.mean, sizeof(double) * (size_t)nslots);
+  std::memcpy(cov, res.cov, sizeof(double) * (size_t)nslots * (size_t)nslots);
+  return SAMSIM_OK;
+}
+
+int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request *rq, int32_t predictor_slot, int32_t group,
+                                  samsim_pair_stat *out) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !rq || !out) return SAMSIM_ERR_ARG;
+  int rc = check_profile_request(h, rq);
+  if (rc) return rc;
+  if (!good_slot(predictor_slot)) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  if (!h->d_sens) HIPCHK(hipMalloc(&h->d_sens, kSensScratch));
+  SensProfPartial *d_part = (SensProfPartial *)h->d_sens;
+  samsim_pair_stat *d_out = (samsim_pair_stat *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
+  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
+  const double *x = predictor_slot == SAMSIM_STAT_N_ACTIVE ? nullptr : h->scal + (size_t)predictor_slot * (size_t)h->ncol;
+  // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
+  // the next pass writes them
+  for (int i = 0; i < rq->narrays; ++i)
+    for (int b0 = 0; b0 < rq->nbins; b0 += DEV_PROF_BINS) {
+      const int nb = rq->nbins - b0 < DEV_PROF_BINS ? rq->nbins - b0 : DEV_PROF_BINS;
+      HIPCHK(samsim_launch_profile_regression(h->lay, x, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol,
+                                              h->cfg.nlayer, rq->axis, rq->origin, rq->arrays[i], b0, nb, rq->nbins, depth ? rq->z0 : 0.0,
+                                              depth ? rq->dz : 1.0, d_part, d_out + (size_t)i * rq->nbins + b0, h->stream));
+    }
+  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_pair_stat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }

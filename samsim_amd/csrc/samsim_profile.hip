@@ -12,66 +12,13 @@
 #include <hip/hip_runtime.h>
 
 #include "samsim_device.h"
+#include "samsim_profile_fold.h"
 #include "samsim_profile_walk.h"
 
 namespace {
 
-using namespace profile_walk;   // the block walk both reductions share (samsim_profile_walk.h)
-
-// running statistics of one bin in one lane: n values with mean `mean` and sum of squared deviations `m2`
-struct Run {
-  long long n;
-  double mean, m2, mn, mx;
-};
-
-// Chan et al.: (n, mean, M2) of the union of two sets from those of the sets; b is not empty
-__device__ __forceinline__ void merge(Run &a, long long nb, double mean_b, double m2_b, double mn_b, double mx_b) {
-  if (a.n == 0) {
-    a.n = nb; a.mean = mean_b; a.m2 = m2_b; a.mn = mn_b; a.mx = mx_b;
-    return;
-  }
-  const long long n = a.n + nb;
-  const double delta = mean_b - a.mean;
-  const double fb = (double)nb / (double)n;
-  a.mean = a.mean + delta * fb;
-  a.m2 = a.m2 + m2_b + delta * delta * ((double)a.n * fb);
-  a.n = n;
-  a.mn = mn_b < a.mn ? mn_b : a.mn;
-  a.mx = mx_b > a.mx ? mx_b : a.mx;
-}
-
-// Lane j folds row j of the tile: the values of bin j of the columns whose bit j is set in their lane's mask, in lane order.
-// The block's mean is formed around the first value (identical columns give it back exactly), the squared deviations in a
-// second walk over the row.
-__device__ __forceinline__ void fold_tile(const double *tile, unsigned long long *smask, unsigned long long mask, int lane, Run &run) {
-  smask[lane] = mask;
-  __syncthreads();
-  long long n = 0;
-  double ref = 0.0, s = 0.0, mn = 1.0e300, mx = -1.0e300;
-  const double *row = tile + lane * kTileStride;
-#pragma unroll 8
-  for (int i = 0; i < 64; ++i) {
-    const bool ok = (smask[i] >> lane) & 1ull;
-    const double v = row[i];
-    ref = (ok && n == 0) ? v : ref;
-    s += ok ? v - ref : 0.0;
-    mn = (ok && v < mn) ? v : mn;
-    mx = (ok && v > mx) ? v : mx;
-    n += ok ? 1 : 0;
-  }
-  if (n > 0) {
-    const double mean = ref + s / (double)n;
-    double m2 = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < 64; ++i) {
-      const bool ok = (smask[i] >> lane) & 1ull;
-      const double d = row[i] - mean;
-      m2 += ok ? d * d : 0.0;
-    }
-    merge(run, n, mean, m2, mn, mx);
-  }
-  __syncthreads();
-}
+using namespace profile_walk;   // the block walk the reductions share (samsim_profile_walk.h)
+using namespace profile_fold;   // Run, merge and fold_tile, shared with the regressions of samsim_sens.hip (samsim_profile_fold.h)
 
 __device__ __forceinline__ void store_partials(ProfPartial *part, int lane, const Run &run) {
   ProfPartial p;
@@ -89,11 +36,12 @@ __global__ void __launch_bounds__(64) profile_layer_kernel(const double *__restr
   const int lane = threadIdx.x;
   const long long nblk = (ncol + 63) / 64;
   Run run{0, 0.0, 0.0, 0.0, 0.0};
+  Co none{0.0, 0.0, 0.0};   // no predictor rides along
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
     TileSink sink{tile, lane, 0};
     layer_block(lay, ncol, N, blk, lane, na, origin, array, b0, nb, sink);
-    fold_tile(tile, smask, sink.mask, lane, run);
+    fold_tile<false>(tile, nullptr, smask, sink.mask, lane, run, none);
   }
   store_partials(part, lane, run);
 }
@@ -108,11 +56,12 @@ __global__ void __launch_bounds__(64) profile_depth_kernel(const double *__restr
   const int lane = threadIdx.x;
   const long long nblk = (ncol + 63) / 64;
   Run run{0, 0.0, 0.0, 0.0, 0.0};
+  Co none{0.0, 0.0, 0.0};   // no predictor rides along
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
     TileSink sink{tile, lane, 0};
     depth_block(lay, ncol, N, blk, lane, na, origin, array, b0, nb, lead, z0, dz, sink);
-    fold_tile(tile, smask, sink.mask, lane, run);
+    fold_tile<false>(tile, nullptr, smask, sink.mask, lane, run, none);
   }
   store_partials(part, lane, run);
 }
