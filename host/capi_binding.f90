@@ -81,6 +81,18 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: mean_x, mean_y, var_x, var_y, cov
   END TYPE samsim_pair_stat
 
+  ! samsim_set_tracks: enum samsim_observable_kind, enum samsim_track_field (0-based rows of a track) and the description of one track
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_OBS_SCALAR = 0, SAMSIM_OBS_N_ACTIVE = 1, SAMSIM_OBS_ICE_THICKNESS = 2, &
+                                   SAMSIM_OBS_BULK_SALINITY = 3, SAMSIM_OBS_LAYER = 4
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_TF_N = 0, SAMSIM_TF_LAST = 1, SAMSIM_TF_MEAN = 2, SAMSIM_TF_M2 = 3, SAMSIM_TF_MIN = 4, &
+                                   SAMSIM_TF_STEP_MIN = 5, SAMSIM_TF_MAX = 6, SAMSIM_TF_STEP_MAX = 7, SAMSIM_TF_N_HOLD = 8, &
+                                   SAMSIM_TF_STEP_FIRST = 9, SAMSIM_TF_STEP_LAST = 10, SAMSIM_NTF = 11
+  INTEGER, PARAMETER :: SAMSIM_MAX_TRACKS = 8
+  TYPE, BIND(C) :: samsim_track_spec
+     INTEGER(c_int32_t) :: struct_size, kind, id, layer, sense, reserved
+     REAL(c_double)     :: threshold
+  END TYPE samsim_track_spec
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -272,6 +284,35 @@ MODULE mo_samsim_capi
        INTEGER(c_int32_t), VALUE :: predictor_slot, group
        TYPE(samsim_pair_stat), INTENT(out) :: out(*)
      END FUNCTION
+     !> follow ntracks observables of every column through the run, sampled after each step that brings the step count to a multiple
+     !! of every; ntracks = 0 with c_null_ptr removes tracking
+     INTEGER(c_int) FUNCTION samsim_set_tracks(h, ntracks, specs, every) BIND(C, name='samsim_set_tracks')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: ntracks
+       TYPE(c_ptr), VALUE :: specs                       ! samsim_track_spec [ntracks] (c_loc of a TARGET array), or c_null_ptr
+       INTEGER(c_int64_t), VALUE :: every
+     END FUNCTION
+     INTEGER(c_int) FUNCTION samsim_reset_tracks(h) BIND(C, name='samsim_reset_tracks')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+     END FUNCTION
+     !> the rows of one track (0-based) for the columns [col0, col0+ncols): out(ncols, SAMSIM_NTF), column fastest
+     INTEGER(c_int) FUNCTION samsim_get_tracks(h, track, col0, ncols, out) BIND(C, name='samsim_get_tracks')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: track
+       INTEGER(c_int64_t), VALUE :: col0, ncols
+       REAL(c_double), INTENT(out) :: out(*)
+     END FUNCTION
+     !> restart: puts back what samsim_get_tracks returned (after samsim_set_tracks)
+     INTEGER(c_int) FUNCTION samsim_set_track_state(h, track, col0, ncols, in) BIND(C, name='samsim_set_track_state')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: track
+       INTEGER(c_int64_t), VALUE :: col0, ncols
+       REAL(c_double), INTENT(in) :: in(*)
+     END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')
        IMPORT
@@ -331,5 +372,12 @@ CONTAINS
     PRINT *, 'samsim C-ABI error in ', what, ': code', rc, ' ', msg(1:n-1)
     STOP 3
   END SUBROUTINE samsim_check
+
+  !> SAMSIM_TRACK_SLOT(track, field): the row of a track (both 0-based) as a slot of the ensemble reductions
+  PURE FUNCTION samsim_track_slot(track, field) RESULT(slot)
+    INTEGER(c_int32_t), INTENT(in) :: track, field
+    INTEGER(c_int32_t) :: slot
+    slot = 65536_c_int32_t + track*32_c_int32_t + field
+  END FUNCTION samsim_track_slot
 
 END MODULE mo_samsim_capi

@@ -5,7 +5,7 @@
 !!
 !! New surface the reference does not have (SURVEY.md, introduction): a namelist file `samsim.nml`
 !!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites,
-!!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens /
+!!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every /
 !! (col0 / ncol_total: this process owns the global columns col0 .. col0+ncol-1 of an ensemble of ncol_total -- one host
 !! process per GPU, contiguous column ranges, no exchange between them, SURVEY.md section 8e)
 !!   &samsim_flags <any flag of mo_data.f90:136-155 or scalar set by mo_init> /       (overrides init(testcase))
@@ -39,6 +39,7 @@ MODULE mo_data
   INTEGER             :: hist_bins = 0       !< > 0: histogram of the ice thickness over the ensemble in hist_bins bins at every output point (dat_ens_hist_thickness.dat)
   REAL(wp)            :: hist_max = 0._wp    !< upper edge of the last bin [m]: edges j*hist_max/hist_bins, j = 0..hist_bins
   LOGICAL             :: sens = .FALSE.      !< sensitivities to the perturbation at every output point: slopes and correlations on dT2m and precip_scale (dat_ens_sens.dat, dat_ens_sens_profile_*.dat)
+  INTEGER(c_int64_t)  :: track_every = 0     !< > 0: time-domain diagnostics, sampled on the device after every track_every-th step: the ice thickness, and the surface temperature with the condition T_top >= 0 (dat_ens_track.dat at the end of the run)
   LOGICAL             :: by_site = .FALSE.   !< stats_by_site asked for and the run has more than one site: the handle carries the sites as group labels
   INTEGER             :: i_time, i_time_out
   REAL(wp)            :: fl_q_bottom = 0._wp, T_top = 0._wp, fl_sw = 0._wp, fl_rest = 0._wp, T2m = 0._wp, tank_depth = 0._wp
@@ -617,6 +618,46 @@ CONTAINS
     DEALLOCATE(q)
   END SUBROUTINE output_sens
 
+  !> The two tracks of track_every > 0 (samsim_set_tracks): track 0 the ice thickness without a condition, track 1 the surface
+  !! temperature with the condition T_top >= 0 -- the melt season: N_HOLD samples long, beginning at step STEP_FIRST.  Set after the
+  !! state (and a restart's), sampled by the library behind the steps that bring the step count to a multiple of track_every.
+  SUBROUTINE tracks_begin(h)
+    TYPE(c_ptr), INTENT(in) :: h
+    TYPE(samsim_track_spec), TARGET :: specs(2)
+    IF (track_every <= 0) RETURN
+    specs%struct_size = INT(c_sizeof(specs(1)), c_int32_t)
+    specs%id = 0; specs%layer = 0; specs%sense = 0; specs%reserved = 0; specs%threshold = 0._wp
+    specs(1)%kind = SAMSIM_OBS_ICE_THICKNESS
+    specs(2)%kind = SAMSIM_OBS_SCALAR; specs(2)%id = INT(S_T_TOP - 1, c_int32_t); specs(2)%sense = 1
+    CALL samsim_check(samsim_set_tracks(h, 2_c_int32_t, c_loc(specs), track_every), 'samsim_set_tracks')
+  END SUBROUTINE tracks_begin
+
+  !> dat_ens_track.dat, written once at the end of a run with track_every > 0: one row per (track, field), the fields MEAN, MAX,
+  !! STEP_MAX, N_HOLD and STEP_FIRST of the two tracks of tracks_begin -- the 0-based track, the field (enum samsim_track_field),
+  !! then count, mean, min, max and standard deviation of that row over the ensemble (samsim_get_ensemble_stats on the track slots).
+  SUBROUTINE output_tracks(h)
+    TYPE(c_ptr), INTENT(in) :: h
+    INTEGER(c_int32_t), PARAMETER :: fields(5) = (/ SAMSIM_TF_MEAN, SAMSIM_TF_MAX, SAMSIM_TF_STEP_MAX, SAMSIM_TF_N_HOLD, SAMSIM_TF_STEP_FIRST /)
+    INTEGER(c_int32_t) :: slots(10)
+    TYPE(samsim_stat)  :: q(10)
+    INTEGER :: t, f, j
+    IF (track_every <= 0) RETURN
+    DO t = 0, 1
+       DO f = 1, 5
+          slots(5*t + f) = samsim_track_slot(INT(t, c_int32_t), fields(f))
+       END DO
+    END DO
+    CALL samsim_check(samsim_get_ensemble_stats(h, 10_c_int32_t, slots, q), 'samsim_get_ensemble_stats')
+    OPEN(62, file='./output/dat_ens_track.dat', STATUS='replace', Recl=256)
+    DO t = 0, 1
+       DO f = 1, 5
+          j = 5*t + f
+          WRITE(62, '(2I4,I10,4ES16.8)') t, fields(f), q(j)%count, q(j)%mean, q(j)%min, q(j)%max, q(j)%std
+       END DO
+    END DO
+    CLOSE(62)
+  END SUBROUTINE output_tracks
+
   !> the units of dat_ens_profile_{T,S_bu,psi_l}_site<kk>.dat: array a = 1..3 of site s = 1..nsites.  nsites is at most
   !! SIZE(sites) = 16 (the namelist holds no more directories), so the units stay within 601..648 and <kk> within two digits.
   INTEGER FUNCTION site_unit(a, s)
@@ -898,6 +939,7 @@ CONTAINS
     END IF
     CALL samsim_check(samsim_set_state(h, st, 0_c_int64_t), 'samsim_set_state')
     IF (LEN_TRIM(restart_in) > 0) CALL read_restart(h, restart_in)
+    CALL tracks_begin(h)
     CALL samsim_check(samsim_set_output_window(h, INT(out_col - 1, c_int64_t), 1_c_int64_t), 'samsim_set_output_window')
     ALLOCATE(olay(1, cfg%nlayer, SAMSIM_NARR), oscal(1, SAMSIM_NSCAL), ona(1))
     o%ncols = 1; o%nlayer = cfg%nlayer; o%reserved = 0
@@ -955,6 +997,7 @@ CONTAINS
          REAL(count1 - count0, wp)/REAL(rate, wp), ' s  (', REAL(colsteps, wp)/(REAL(count1 - count0, wp)/REAL(rate, wp)), &
          ' column-timesteps/s)'
     IF (LEN_TRIM(restart_out) > 0) CALL write_restart(h, restart_out)
+    CALL output_tracks(h)
     CALL output_end()
     CALL samsim_destroy(h)
     CALL sub_deallocate()
@@ -970,7 +1013,7 @@ PROGRAM SAMSIM
   CHARACTER*12000 :: description
   LOGICAL         :: have_nml
   NAMELIST /samsim_run/ testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, &
-       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens
+       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every
 
   testcase    = 1
   description = 'MI355X-native batched column solver'

@@ -442,6 +442,77 @@ int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots
 int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request *rq, int32_t predictor_slot,
                                   int32_t group, samsim_pair_stat *out /*[narrays][nbins]*/);
 
+/* Time-domain diagnostics: per-column tracks sampled on the device.  Everything above describes the ensemble at one moment; a track
+ * follows one observable of every column THROUGH the run and keeps eleven numbers per column -- the annual maximum of the ice
+ * thickness and when it is reached, the first and last step at which a condition held (melt onset, freeze-up), for how many samples
+ * it held (the length of the melt season), the mean and variance over time -- without a samsim_get_state per look.  The entry points
+ * below were added without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only, found by symbol as the group, histogram and
+ * sensitivity functions are.
+ *
+ *   Observable x of a column at a sample, computed from the state samsim_get_state would return at that moment.
+ *     SAMSIM_OBS_SCALAR: the stored slot `id` (enum samsim_scalar).  SAMSIM_OBS_N_ACTIVE: (double)n_active.
+ *     SAMSIM_OBS_ICE_THICKNESS: Z_Na of the profile statistics, Z_0 = 0, Z_k = Z_{k-1} + thick(k) by sequential double additions, k
+ *     ascending.  SAMSIM_OBS_BULK_SALINITY: (sum_k S_abs(k)) / (sum_k m(k)), both sums sequential over k = 1..Na, then one IEEE
+ *     division; with a zero mass sum the quotient is whatever IEEE gives.  SAMSIM_OBS_LAYER: the value of array `id` (enum
+ *     samsim_layer_array) in the addressed layer, exactly as samsim_get_state returns it (for SAMSIM_A_S_BU S_abs/m where m != 0):
+ *     layer k >= 1 counts from the top (layer k), k <= -1 from the bottom (layer Na + 1 + k).  A LAYER track whose layer does not
+ *     exist in a column (k > Na or Na + 1 + k < 1) is not sampled for that column at that moment: none of its fields change.
+ *   When samples are taken.  After the step that brings clock.step to s, whenever s % every == 0: sampling is tied to the absolute
+ *     step count, not to the steps since samsim_set_tracks.  Every column with status == 0 at that moment is sampled with sample time
+ *     s; stopped columns are never sampled, nor is the state before the first step.  How the caller cuts its samsim_step calls and how
+ *     samsim_set_launch_split is set do not change a byte of any track (a call is cut into launches at the sample points inside it,
+ *     and the run is bit-for-bit independent of where launches are cut); tracking does not change a byte of the state, the status,
+ *     the clock, the work counters or the output snapshot.  samsim_steps_timed times the samples with the steps.
+ *   Fields.  One double[ncol] row per track and field (enum samsim_track_field).  Initial values: N = 0, LAST = 0, MEAN = 0, M2 = 0,
+ *     MIN = +inf, STEP_MIN = -1, MAX = -inf, STEP_MAX = -1, N_HOLD = 0, STEP_FIRST = -1, STEP_LAST = -1.  Update at a sample with value x
+ *     and time s, in this order:
+ *       N += 1;  LAST = x;  d = x - MEAN;  MEAN = MEAN + d / N (an IEEE division);  M2 = M2 + d * (x - MEAN) (the new MEAN; the
+ *       product is rounded, then the sum; no fused multiply-add);
+ *       if x < MIN: MIN = x, STEP_MIN = s;   if x > MAX: MAX = x, STEP_MAX = s;
+ *       if the condition holds (sense +1: x >= threshold; sense -1: x < threshold; sense 0: never): N_HOLD += 1; if STEP_FIRST < 0:
+ *       STEP_FIRST = s; STEP_LAST = s.
+ *     The first attainment of an extreme is kept.  A NaN never becomes an extreme and never satisfies a condition.  Step numbers are
+ *     stored as doubles, exact below 2^53.  The update of a column is a fixed sequence of IEEE operations on that column's own data, no
+ *     cross-lane arithmetic: every field is reproducible to the bit by a host that applies the same sequence to samsim_get_state at
+ *     the same moments.  The time variance is M2 / N, dates are STEP_* * dt: the host forms both.
+ *   samsim_set_tracks.  ntracks in 1..SAMSIM_MAX_TRACKS, every >= 1: allocates [ntracks][SAMSIM_NTF][ncol] doubles on the device and
+ *     sets them to the initial values.  ntracks == 0 with NULL removes tracking and frees the rows (also when none was set).  A call
+ *     that is refused leaves the previous tracks in force.  samsim_reset_tracks sets the initial values again.  samsim_set_state,
+ *     samsim_set_status and samsim_set_clock leave the rows alone; samsim_destroy frees them.  The rows are not part of a checkpoint:
+ *     for a restart samsim_get_tracks and samsim_set_track_state move the window [col0, col0 + ncols) of one track, [SAMSIM_NTF][ncols];
+ *     a restart sets the tracks first and then puts the rows back.
+ *   Track rows as slots.  Wherever a slot is accepted -- samsim_get_ensemble_stats, samsim_get_group_stats, samsim_get_histogram, the
+ *     slots of samsim_get_covariance, predictor_slot of samsim_get_profile_regression -- SAMSIM_TRACK_SLOT(track, field) is accepted
+ *     too, with track < ntracks and field < SAMSIM_NTF of the tracks in force, and resolves to that row; without tracks, or out of
+ *     range, it is the SAMSIM_ERR_ARG of any bad slot.  So the distribution of the onset date over the ensemble is a histogram of
+ *     STEP_FIRST (with v0 = 0, entry 0 holds the columns in which it never happened), its statistics per site a samsim_get_group_stats,
+ *     its covariance with dT2m a samsim_get_covariance; and a track of ICE_THICKNESS with `every` equal to the launch length gives
+ *     the reductions a current thickness through LAST, where SAMSIM_S_THICKNESS holds the last output point's.
+ *   Errors, all found before any device work, in this order.  samsim_set_tracks: SAMSIM_ERR_ARG for h NULL; ntracks out of range;
+ *     specs NULL with ntracks > 0; every < 1 with ntracks > 0; then per spec in order: SAMSIM_ERR_ABI for a wrong struct_size;
+ *     SAMSIM_ERR_ARG for a bad kind or a bad id for the kind; layer == 0 or |layer| > nlayer with LAYER; a non-zero layer or id where
+ *     the kind takes none; sense outside {-1, 0, 1}; a non-finite threshold with sense != 0; reserved != 0.  SAMSIM_ERR_NOMEM if the rows
+ *     cannot be allocated (the previous tracks stay).  The other three: SAMSIM_ERR_ARG for NULL pointers, no tracks set, a track
+ *     outside [0, ntracks), a window outside [0, ncol). */
+#define SAMSIM_MAX_TRACKS 8
+enum samsim_observable_kind { SAMSIM_OBS_SCALAR = 0, SAMSIM_OBS_N_ACTIVE, SAMSIM_OBS_ICE_THICKNESS, SAMSIM_OBS_BULK_SALINITY, SAMSIM_OBS_LAYER };
+enum samsim_track_field { SAMSIM_TF_N = 0, SAMSIM_TF_LAST, SAMSIM_TF_MEAN, SAMSIM_TF_M2, SAMSIM_TF_MIN, SAMSIM_TF_STEP_MIN,
+                          SAMSIM_TF_MAX, SAMSIM_TF_STEP_MAX, SAMSIM_TF_N_HOLD, SAMSIM_TF_STEP_FIRST, SAMSIM_TF_STEP_LAST, SAMSIM_NTF };
+typedef struct samsim_track_spec {
+  int32_t struct_size; /* = sizeof(samsim_track_spec) */
+  int32_t kind;        /* enum samsim_observable_kind */
+  int32_t id;          /* SCALAR: enum samsim_scalar; LAYER: enum samsim_layer_array; else 0 */
+  int32_t layer;       /* LAYER: k >= 1 counts from the top (layer k), k <= -1 from the bottom (layer Na + 1 + k); else 0 */
+  int32_t sense;       /* 0 no condition, +1 holds when x >= threshold, -1 holds when x < threshold */
+  int32_t reserved;    /* 0 */
+  double  threshold;   /* finite when sense != 0 */
+} samsim_track_spec;
+int samsim_set_tracks(samsim_handle *h, int32_t ntracks, const samsim_track_spec *specs, int64_t every);
+int samsim_reset_tracks(samsim_handle *h);
+int samsim_get_tracks(samsim_handle *h, int32_t track, int64_t col0, int64_t ncols, double *out /*[SAMSIM_NTF][ncols]*/);
+int samsim_set_track_state(samsim_handle *h, int32_t track, int64_t col0, int64_t ncols, const double *in /*[SAMSIM_NTF][ncols]*/);
+#define SAMSIM_TRACK_SLOT(track, field) (0x10000 + (track) * 32 + (field))
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

@@ -138,6 +138,45 @@ def slope_and_correlation(pair_stats):
     return slope, np.where(ok, c / np.where(ok, scale, 1.0), 0.0)
 
 
+MAX_TRACKS = 8              # SAMSIM_MAX_TRACKS
+# enum samsim_observable_kind
+OBSERVABLES = ["scalar", "n_active", "ice_thickness", "bulk_salinity", "layer"]
+OBS = {n: i for i, n in enumerate(OBSERVABLES)}
+# enum samsim_track_field: one double[ncol] row per track and field
+TRACK_FIELDS = ["N", "LAST", "MEAN", "M2", "MIN", "STEP_MIN", "MAX", "STEP_MAX", "N_HOLD", "STEP_FIRST", "STEP_LAST"]
+TF = {n: i for i, n in enumerate(TRACK_FIELDS)}
+NTF = len(TRACK_FIELDS)
+TRACK_INITIAL = {"N": 0.0, "LAST": 0.0, "MEAN": 0.0, "M2": 0.0, "MIN": np.inf, "STEP_MIN": -1.0, "MAX": -np.inf, "STEP_MAX": -1.0,
+                 "N_HOLD": 0.0, "STEP_FIRST": -1.0, "STEP_LAST": -1.0}
+
+
+class TrackSpec(C.Structure):
+    """samsim_track_spec: one observable followed through the run, with an optional condition x >= threshold (sense +1) or
+    x < threshold (sense -1)"""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("id", C.c_int32), ("layer", C.c_int32), ("sense", C.c_int32),
+                ("reserved", C.c_int32), ("threshold", C.c_double)]
+
+    @staticmethod
+    def make(kind, name=None, layer=0, sense=0, threshold=0.0) -> "TrackSpec":
+        """kind from OBSERVABLES; name from SCALARS ("scalar") or ARRAYS ("layer"); layer k >= 1 from the top, k <= -1 from the
+        bottom ("layer" only)"""
+        ident = S[name] if kind == "scalar" else A[name] if kind == "layer" else 0
+        return TrackSpec(C.sizeof(TrackSpec), OBS[kind], ident, int(layer), int(sense), 0, float(threshold))
+
+
+def track_slot(track, field) -> int:
+    """SAMSIM_TRACK_SLOT(track, field): the row of a track as a slot of ensemble_stats, group_stats, histogram, covariance and
+    profile_regression; field a name from TRACK_FIELDS or its number"""
+    return 0x10000 + int(track) * 32 + (TF[field] if isinstance(field, str) else int(field))
+
+
+def _slot(name) -> int:
+    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot gives it"""
+    if isinstance(name, (int, np.integer)):
+        return int(name)
+    return -1 if name == "N_active" else S[name]
+
+
 STAT_DTYPE = np.dtype([("count", np.int64), ("mean", np.float64), ("min", np.float64), ("max", np.float64), ("std", np.float64)])
 
 
@@ -256,6 +295,7 @@ class Solver:
         self._chk(self._create(device), "create")
         self._out_window = (0, 1)
         self.ngroups = 0            # groups of set_groups; 0: no labels
+        self.ntracks = 0            # tracks of set_tracks; 0: no tracking
 
     def _create(self, device):
         f = self._f("create")
@@ -329,6 +369,13 @@ class Solver:
         sens_sig = {"get_covariance": [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p],
                     "get_profile_regression": [vp, C.POINTER(ProfileRequest), C.c_int32, C.c_int32, C.c_void_p]}
         for n, a in sens_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the time-domain diagnostics
+        track_sig = {"set_tracks": [vp, C.c_int32, C.POINTER(TrackSpec), i64], "reset_tracks": [vp],
+                     "get_tracks": [vp, C.c_int32, i64, i64, C.c_void_p], "set_track_state": [vp, C.c_int32, i64, i64, C.c_void_p]}
+        for n, a in track_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -485,9 +532,10 @@ class Solver:
         return a, b
 
     def ensemble_stats(self, names):
-        """{name: Stat} over the columns without a STOP code; names from SCALARS or "N_active" (samsim_get_ensemble_stats)"""
+        """{name: Stat} over the columns without a STOP code; names from SCALARS, "N_active" or ints of track_slot
+        (samsim_get_ensemble_stats)"""
         names = list(names)
-        slots = (C.c_int32 * len(names))(*[-1 if n == "N_active" else S[n] for n in names])
+        slots = (C.c_int32 * len(names))(*[_slot(n) for n in names])
         out = (Stat * len(names))()
         self._chk(self._f("get_ensemble_stats")(self._h, len(names), slots, out), "get_ensemble_stats")
         return {n: out[i] for i, n in enumerate(names)}
@@ -512,10 +560,10 @@ class Solver:
 
     def group_stats(self, names):
         """{name: structured array [ngroups] with fields count, mean, min, max, std} over the columns without a STOP code, per
-        group of set_groups; names from SCALARS or "N_active" (samsim_get_group_stats)"""
+        group of set_groups; names from SCALARS, "N_active" or ints of track_slot (samsim_get_group_stats)"""
         names = list(names)
         ng = self.ngroups
-        slots = (C.c_int32 * len(names))(*[-1 if n == "N_active" else S[n] for n in names])
+        slots = (C.c_int32 * len(names))(*[_slot(n) for n in names])
         out = np.zeros((len(names), max(1, ng)), dtype=STAT_DTYPE)
         self._chk(self._f("get_group_stats")(self._h, len(names), slots, out.ctypes.data), "get_group_stats")
         return {n: out[i] for i, n in enumerate(names)}
@@ -566,11 +614,11 @@ class Solver:
         return buf if by_group == 1 else buf[0]
 
     def histogram(self, name, nvbins, v0, dv, by_group=False) -> np.ndarray:
-        """fixed-edge histogram of a scalar from SCALARS or "N_active" over the columns without a STOP code
+        """fixed-edge histogram of a scalar from SCALARS, of "N_active" or of a track row (an int of track_slot) over the columns without a STOP code
         (samsim_get_histogram): edges v0 + j dv, j = 0..nvbins; entry 0 counts the values below the first edge, entry j+1 those
         in [E_j, E_{j+1}), entry nvbins+1 those at or above the last edge.  int64 [nvbins+2]; by_group: [ngroups, nvbins+2] per
         group of set_groups"""
-        return self.histogram_raw(-1 if name == "N_active" else S[name], hist_bins(nvbins, v0, dv), 1 if by_group else 0)
+        return self.histogram_raw(_slot(name), hist_bins(nvbins, v0, dv), 1 if by_group else 0)
 
     def profile_histogram_raw(self, rq: ProfileRequest, vb: HistBins, group=-1) -> np.ndarray:
         """samsim_get_profile_histogram with the arguments as given (no checks on this side): int64 [nbins, nvbins+2]"""
@@ -600,10 +648,10 @@ class Solver:
         return int(count.value), mean, cov
 
     def covariance(self, names, group=None):
-        """(count, mean [n], cov [n, n]) of the scalars `names` (from SCALARS, or "N_active") over the columns without a STOP code --
+        """(count, mean [n], cov [n, n]) of the scalars `names` (from SCALARS, "N_active", or ints of track_slot) over the columns without a STOP code --
         with group: over those with that label of set_groups -- (samsim_get_covariance): population covariances, the diagonal the
         variances; capi.correlation(cov) gives the correlations"""
-        return self.covariance_raw([-1 if n == "N_active" else S[n] for n in names], -1 if group is None else int(group))
+        return self.covariance_raw([_slot(n) for n in names], -1 if group is None else int(group))
 
     def profile_regression_raw(self, rq: ProfileRequest, predictor_slot, group=-1) -> np.ndarray:
         """samsim_get_profile_regression with the arguments as given (no checks on this side): PAIR_STAT_DTYPE [narrays][nbins]"""
@@ -616,14 +664,46 @@ class Solver:
 
     def profile_regression(self, names, predictor, axis="layer", origin="top", nbins=None, z0=0.0, dz=None, group=None):
         """{name: PAIR_STAT_DTYPE array [nbins]}: per bin of profile_stats the joint moments of the bin value y of the array and the
-        column's scalar `predictor` x (from SCALARS, or "N_active") over the columns that contribute to the bin
+        column's scalar `predictor` x (from SCALARS, "N_active", or an int of track_slot) over the columns that contribute to the bin
         (samsim_get_profile_regression); capi.slope_and_correlation gives dy/dx and the correlation per bin"""
         names = list(names)
         if axis == "depth" and (nbins is None or dz is None):
             raise ValueError("axis='depth' needs nbins and dz")
         rq = self._profile_request(names, axis, origin, nbins, z0, dz)
-        out = self.profile_regression_raw(rq, -1 if predictor == "N_active" else S[predictor], -1 if group is None else int(group))
+        out = self.profile_regression_raw(rq, _slot(predictor), -1 if group is None else int(group))
         return {n: out[i] for i, n in enumerate(names)}
+
+    # -- time-domain diagnostics
+    def set_tracks_raw(self, ntracks, specs, every):
+        """samsim_set_tracks with the arguments as given (no checks on this side): specs a ctypes array of TrackSpec or None"""
+        self._chk(self._f("set_tracks")(self._h, int(ntracks), specs, int(every)), "set_tracks")
+        self.ntracks = int(ntracks) if specs is not None else 0
+
+    def set_tracks(self, specs, every=1):
+        """follow the observables `specs` (TrackSpec, at most MAX_TRACKS) through the run: from now on every column without a
+        STOP code is sampled after each step that brings clock.step to a multiple of `every` (samsim_set_tracks).  The rows start
+        from TRACK_INITIAL.  set_tracks(None) removes tracking"""
+        if specs is None:
+            return self.set_tracks_raw(0, None, 0)
+        specs = list(specs)
+        self.set_tracks_raw(len(specs), (TrackSpec * max(1, len(specs)))(*specs), every)
+
+    def reset_tracks(self):
+        """the rows of every track back to TRACK_INITIAL (samsim_reset_tracks)"""
+        self._chk(self._f("reset_tracks")(self._h), "reset_tracks")
+
+    def tracks(self, track, col0: int = 0, ncols: int | None = None):
+        """{field: float64 [ncols]} of one track, fields from TRACK_FIELDS (samsim_get_tracks)"""
+        n = self.ncol - col0 if ncols is None else ncols
+        buf = np.zeros((NTF, max(0, n)))
+        self._chk(self._f("get_tracks")(self._h, int(track), col0, n, buf.ctypes.data), "get_tracks")
+        return {f: buf[i] for i, f in enumerate(TRACK_FIELDS)}
+
+    def set_track_state(self, track, fields, col0: int = 0):
+        """restart: put back what tracks() returned for the columns [col0, col0 + ncols) of one track (samsim_set_track_state);
+        set_tracks comes first"""
+        buf = np.ascontiguousarray(np.stack([np.asarray(fields[f], dtype=np.float64) for f in TRACK_FIELDS]))
+        self._chk(self._f("set_track_state")(self._h, int(track), col0, buf.shape[1], buf.ctypes.data), "set_track_state")
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

@@ -18,6 +18,7 @@
 #include "samsim_groups.h"
 #include "samsim_hist.h"
 #include "samsim_sens.h"
+#include "samsim_tracks.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
 // samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS) over every column
@@ -73,6 +74,10 @@ struct samsim_handle {
   void *d_group = nullptr;     // samsim_get_group_stats: the waves' partials of one slot, then its results (kGroupScratch bytes)
   void *d_hist = nullptr;      // samsim_get_histogram / samsim_get_profile_histogram: the 64-bit counts of one request (kHistScratch bytes)
   void *d_sens = nullptr;      // samsim_get_covariance / samsim_get_profile_regression: the waves' partials of one pass, then the results (kSensScratch bytes)
+  double *tracks = nullptr;    // [ntracks][SAMSIM_NTF][ncol] rows of the time-domain diagnostics (samsim_set_tracks), sampled by launch()
+  int32_t ntracks = 0;         // 0: no tracking
+  long long track_every = 0;   // a sample follows the step that brings clk.step to a multiple of it
+  TrackDev track[SAMSIM_MAX_TRACKS]{};
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -313,7 +318,9 @@ void advance_clock(samsim_handle *h, long long nsteps) {
   }
 }
 
-int launch(samsim_handle *h, long long nsteps) {
+// one launch of nsteps steps (two from split_blocks blocks up); with `sample` each part's launch is followed, on its own stream, by
+// the sampling kernel of the tracks for that part's blocks
+int launch_cut(samsim_handle *h, long long nsteps, bool sample) {
   if (nsteps <= 0) return SAMSIM_OK;
   // the forcing tables are read whenever atmoflux_flag is 2 (T2m / precipitation in every step, the radiative fluxes with
   // boundflux_flag 2): no launch without them, whatever the other flags say
@@ -362,10 +369,56 @@ int launch(samsim_handle *h, long long nsteps) {
     HIPCHK(hipMemcpyAsync(&h->d_params[s], &p, sizeof(DevParams), hipMemcpyHostToDevice, st));
     HIPCHK(samsim_launch_step(&h->d_params[s], &p, nb, st));
     HIPCHK(hipEventRecord(h->slot_done[s], st));
+    if (sample) {
+      // directly behind the step launch of the same blocks on the same stream: the columns of a part are independent of the other
+      // part's, so the sample waits for nothing else
+      TrackParams tp{};
+      tp.lay = h->lay; tp.scal = h->scal; tp.n_active = h->n_active; tp.status = h->status; tp.flags = h->flags;
+      tp.rows = h->tracks;
+      tp.ncol = h->ncol; tp.block0 = b0;
+      tp.step = (double)(h->clk.step + nsteps);
+      tp.N = h->cfg.nlayer; tp.ntracks = h->ntracks;
+      for (int t = 0; t < h->ntracks; ++t) {
+        tp.t[t] = h->track[t];
+        if (h->track[t].kind == SAMSIM_OBS_ICE_THICKNESS) tp.need_thick = 1;
+        if (h->track[t].kind == SAMSIM_OBS_BULK_SALINITY) tp.need_salt = 1;
+      }
+      HIPCHK(samsim_launch_track_sample(&tp, nb, st));
+    }
   }
   h->stepped = true;
   advance_clock(h, nsteps);
   return SAMSIM_OK;
+}
+
+// nsteps steps.  With tracks in force the call is cut at the sample points inside it (the steps that bring clk.step to a multiple
+// of track_every): each cut ends a launch -- whose last step stores everything, so the sample reads current rows -- and is followed
+// by the sample.  The run does not depend on where launches are cut, bit for bit.  Without tracks, or with no sample point inside
+// the call, this is one launch_cut and the sequence of device calls is what it was before there were tracks.
+int launch(samsim_handle *h, long long nsteps) {
+  if (h->ntracks < 1) return launch_cut(h, nsteps, false);
+  while (nsteps > 0) {
+    const long long to_sample = h->track_every - h->clk.step % h->track_every;
+    const long long n = nsteps < to_sample ? nsteps : to_sample;
+    const int rc = launch_cut(h, n, n == to_sample);
+    if (rc) return rc;
+    nsteps -= n;
+  }
+  return SAMSIM_OK;
+}
+
+// a slot of the statistics: an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE, or SAMSIM_TRACK_SLOT(track, field) of the tracks in force
+bool good_slot(const samsim_handle *h, int32_t slot) {
+  if (slot == SAMSIM_STAT_N_ACTIVE || (slot >= 0 && slot < SAMSIM_NSCAL)) return true;
+  const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
+  return h->tracks && o >= 0 && o / 32 < h->ntracks && o % 32 < SAMSIM_NTF;
+}
+// the [ncol] row of a good slot; null for SAMSIM_STAT_N_ACTIVE (the reductions then read n_active)
+const double *slot_row(const samsim_handle *h, int32_t slot) {
+  if (slot == SAMSIM_STAT_N_ACTIVE) return nullptr;
+  if (slot < SAMSIM_NSCAL) return h->scal + (size_t)slot * (size_t)h->ncol;
+  const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
+  return h->tracks + ((size_t)(o / 32) * SAMSIM_NTF + (size_t)(o % 32)) * (size_t)h->ncol;
 }
 
 // every entry point but the stepping ones waits for the second stream and makes the next launch's second part wait for whatever
@@ -484,7 +537,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->lay); (void)hipFree(h->scal); (void)hipFree(h->n_active); (void)hipFree(h->status);
   (void)hipFree(h->err_layer); (void)hipFree(h->err_step); (void)hipFree(h->work);
   (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
-  (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens);
+  (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens); (void)hipFree(h->tracks);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
   (void)hipFree(h->ocean_dflq); (void)hipFree(h->ocean_sbu);
@@ -875,13 +928,13 @@ int samsim_get_ensemble_stats(samsim_handle *h, int32_t nslots, const int32_t *s
   if (rc) return rc;
   if (nslots < 0 || (nslots > 0 && (!slots || !out))) return SAMSIM_ERR_ARG;
   for (int i = 0; i < nslots; ++i)
-    if (slots[i] != SAMSIM_STAT_N_ACTIVE && (slots[i] < 0 || slots[i] >= SAMSIM_NSCAL)) return SAMSIM_ERR_ARG;
+    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
   if (!h->d_stat) HIPCHK(hipMalloc(&h->d_stat, sizeof(StatPartial) * kStatGrid));
   StatPartial *d_part = (StatPartial *)h->d_stat;
   std::vector<StatPartial> part(kStatGrid);
   const long long nc = h->ncol;
   for (int i = 0; i < nslots; ++i) {
-    const double *row = (slots[i] == SAMSIM_STAT_N_ACTIVE) ? nullptr : h->scal + (size_t)slots[i] * (size_t)nc;
+    const double *row = slot_row(h, slots[i]);
     hipLaunchKernelGGL(stat_kernel<false>, dim3(kStatGrid), dim3(kStatBlock), 0, h->stream, row, h->n_active, h->status, nc, 0.0,
                        d_part);
     HIPCHK(hipMemcpyAsync(part.data(), d_part, sizeof(StatPartial) * kStatGrid, hipMemcpyDeviceToHost, h->stream));
@@ -989,16 +1042,16 @@ int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slot
   if (!h || nslots < 0 || (nslots > 0 && (!slots || !out))) return SAMSIM_ERR_ARG;
   if (!h->groups) return SAMSIM_ERR_ARG;
   for (int i = 0; i < nslots; ++i)
-    if (slots[i] != SAMSIM_STAT_N_ACTIVE && (slots[i] < 0 || slots[i] >= SAMSIM_NSCAL)) return SAMSIM_ERR_ARG;
+    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
   int rc = use(h);
   if (rc) return rc;
   if (!h->d_group) HIPCHK(hipMalloc(&h->d_group, kGroupScratch));
   GroupPartial *d_part = (GroupPartial *)h->d_group;
   samsim_stat *d_out = (samsim_stat *)((char *)h->d_group + kGroupPartBytes);
-  const size_t nc = (size_t)h->ncol, ng = (size_t)h->ngroups;
+  const size_t ng = (size_t)h->ngroups;
   // one pass per slot, all on the handle's stream: a slot's results have left the scratch before the next slot's merge writes them
   for (int i = 0; i < nslots; ++i) {
-    const double *row = (slots[i] == SAMSIM_STAT_N_ACTIVE) ? nullptr : h->scal + (size_t)slots[i] * nc;
+    const double *row = slot_row(h, slots[i]);
     HIPCHK(samsim_launch_group_stats(row, h->n_active, h->status, h->groups, h->ncol, h->ngroups, d_part, d_out, h->stream));
     HIPCHK(hipMemcpyAsync(out + (size_t)i * ng, d_out, sizeof(samsim_stat) * ng, hipMemcpyDeviceToHost, h->stream));
   }
@@ -1029,7 +1082,7 @@ int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins 
   HistEdges e;
   int rc = check_hist_bins(vb, &e);
   if (rc) return rc;
-  if (slot != SAMSIM_STAT_N_ACTIVE && (slot < 0 || slot >= SAMSIM_NSCAL)) return SAMSIM_ERR_ARG;
+  if (!good_slot(h, slot)) return SAMSIM_ERR_ARG;
   if (by_group != 0 && by_group != 1) return SAMSIM_ERR_ARG;
   if (by_group && !h->groups) return SAMSIM_ERR_ARG;
   rc = use(h);
@@ -1037,7 +1090,7 @@ int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins 
   if (!h->d_hist) HIPCHK(hipMalloc(&h->d_hist, kHistScratch));
   const int ng = by_group ? h->ngroups : 1;
   const size_t bytes = sizeof(int64_t) * (size_t)ng * (size_t)(e.nvbins + 2);
-  const double *row = (slot == SAMSIM_STAT_N_ACTIVE) ? nullptr : h->scal + (size_t)slot * (size_t)h->ncol;
+  const double *row = slot_row(h, slot);
   HIPCHK(hipMemsetAsync(h->d_hist, 0, bytes, h->stream));
   HIPCHK(samsim_launch_hist(row, h->n_active, h->status, by_group ? h->groups : nullptr, h->ncol, ng, e,
                             (unsigned long long *)h->d_hist, h->stream));
@@ -1076,8 +1129,6 @@ int samsim_get_profile_histogram(samsim_handle *h, const samsim_profile_request 
   return SAMSIM_OK;
 }
 
-// a slot of the statistics: an enum samsim_scalar, or SAMSIM_STAT_N_ACTIVE
-static bool good_slot(int32_t slot) { return slot == SAMSIM_STAT_N_ACTIVE || (slot >= 0 && slot < SAMSIM_NSCAL); }
 // one group per call: -1 every column, else a label of samsim_set_groups
 static bool good_group(const samsim_handle *h, int32_t group) { return group == -1 || (group >= 0 && h->groups && group < h->ngroups); }
 
@@ -1086,7 +1137,7 @@ int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots
   if (!h || !slots || !count || !mean || !cov) return SAMSIM_ERR_ARG;
   if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
   for (int i = 0; i < nslots; ++i)
-    if (!good_slot(slots[i])) return SAMSIM_ERR_ARG;
+    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
   if (!good_group(h, group)) return SAMSIM_ERR_ARG;
   int rc = use(h);
   if (rc) return rc;
@@ -1094,7 +1145,7 @@ int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots
   double *d_part = (double *)h->d_sens;
   CovResult *d_out = (CovResult *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
   SensRows rows{};
-  for (int i = 0; i < nslots; ++i) rows.row[i] = slots[i] == SAMSIM_STAT_N_ACTIVE ? nullptr : h->scal + (size_t)slots[i] * (size_t)h->ncol;
+  for (int i = 0; i < nslots; ++i) rows.row[i] = slot_row(h, slots[i]);
   HIPCHK(samsim_launch_covariance(rows, nslots, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol, d_part, d_out,
                                   h->stream));
   CovResult res;
@@ -1112,7 +1163,7 @@ int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request
   if (!h || !rq || !out) return SAMSIM_ERR_ARG;
   int rc = check_profile_request(h, rq);
   if (rc) return rc;
-  if (!good_slot(predictor_slot)) return SAMSIM_ERR_ARG;
+  if (!good_slot(h, predictor_slot)) return SAMSIM_ERR_ARG;
   if (!good_group(h, group)) return SAMSIM_ERR_ARG;
   rc = use(h);
   if (rc) return rc;
@@ -1120,7 +1171,7 @@ int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request
   SensProfPartial *d_part = (SensProfPartial *)h->d_sens;
   samsim_pair_stat *d_out = (samsim_pair_stat *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
   const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
-  const double *x = predictor_slot == SAMSIM_STAT_N_ACTIVE ? nullptr : h->scal + (size_t)predictor_slot * (size_t)h->ncol;
+  const double *x = slot_row(h, predictor_slot);
   // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
   // the next pass writes them
   for (int i = 0; i < rq->narrays; ++i)
@@ -1132,6 +1183,115 @@ int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request
     }
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_pair_stat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+// the checks of one track, in the order samsim.h gives
+static int check_track_spec(const samsim_handle *h, const samsim_track_spec &s) {
+  if (s.struct_size != (int32_t)sizeof(samsim_track_spec)) return SAMSIM_ERR_ABI;
+  switch (s.kind) {
+    case SAMSIM_OBS_SCALAR: if (s.id < 0 || s.id >= SAMSIM_NSCAL) return SAMSIM_ERR_ARG; break;
+    case SAMSIM_OBS_LAYER: if (s.id < 0 || s.id >= SAMSIM_NARR) return SAMSIM_ERR_ARG; break;
+    case SAMSIM_OBS_N_ACTIVE: case SAMSIM_OBS_ICE_THICKNESS: case SAMSIM_OBS_BULK_SALINITY: break;
+    default: return SAMSIM_ERR_ARG;
+  }
+  if (s.kind == SAMSIM_OBS_LAYER) {
+    if (s.layer == 0 || s.layer > h->cfg.nlayer || s.layer < -h->cfg.nlayer) return SAMSIM_ERR_ARG;
+  } else if (s.layer != 0 || (s.kind != SAMSIM_OBS_SCALAR && s.id != 0)) {
+    return SAMSIM_ERR_ARG;
+  }
+  if (s.sense < -1 || s.sense > 1) return SAMSIM_ERR_ARG;
+  if (s.sense != 0 && !std::isfinite(s.threshold)) return SAMSIM_ERR_ARG;
+  if (s.reserved != 0) return SAMSIM_ERR_ARG;
+  return SAMSIM_OK;
+}
+
+// the initial values into the rows of nt tracks, enqueued on the handle's stream
+static hipError_t init_tracks(samsim_handle *h, double *rows, int nt) {
+  const size_t nc = (size_t)h->ncol;
+  for (int t = 0; t < nt; ++t)
+    for (int f = 0; f < SAMSIM_NTF; ++f) {
+      const hipError_t e = fill(rows + ((size_t)t * SAMSIM_NTF + (size_t)f) * nc, nc, dev_track_initial(f), h->stream);
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
+}
+
+int samsim_set_tracks(samsim_handle *h, int32_t ntracks, const samsim_track_spec *specs, int64_t every) {
+  // every check first: a call that is refused leaves the previous tracks in force
+  if (!h) return SAMSIM_ERR_ARG;
+  if (ntracks < 0 || ntracks > SAMSIM_MAX_TRACKS) return SAMSIM_ERR_ARG;
+  if (ntracks == 0 && specs) return SAMSIM_ERR_ARG;
+  if (ntracks > 0 && !specs) return SAMSIM_ERR_ARG;
+  if (ntracks > 0 && every < 1) return SAMSIM_ERR_ARG;
+  for (int t = 0; t < ntracks; ++t) {
+    const int rc = check_track_spec(h, specs[t]);
+    if (rc) return rc;
+  }
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the new rows hold their initial values on the device before the handle sees them
+  double *rows = nullptr;
+  if (ntracks > 0) {
+    if (dalloc(&rows, (size_t)ntracks * SAMSIM_NTF * (size_t)h->ncol) != hipSuccess) {
+      (void)hipGetLastError();
+      return SAMSIM_ERR_NOMEM;
+    }
+    if (!hip_ok(init_tracks(h, rows, ntracks), "fill tracks") || !hip_ok(hipStreamSynchronize(h->stream), "sync")) {
+      (void)hipFree(rows);
+      return SAMSIM_ERR_HIP;
+    }
+  }
+  (void)hipFree(h->tracks);
+  h->tracks = rows;
+  h->ntracks = ntracks;
+  h->track_every = ntracks > 0 ? every : 0;
+  for (int t = 0; t < ntracks; ++t) h->track[t] = TrackDev{specs[t].kind, specs[t].id, specs[t].layer, specs[t].sense, specs[t].threshold};
+  return SAMSIM_OK;
+}
+
+int samsim_reset_tracks(samsim_handle *h) {
+  if (!h || !h->tracks) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(init_tracks(h, h->tracks, h->ntracks));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+// the checks samsim_get_tracks and samsim_set_track_state share, in the order samsim.h gives
+static int check_track_window(const samsim_handle *h, const void *buf, int32_t track, int64_t col0, int64_t ncols) {
+  if (!h || !buf) return SAMSIM_ERR_ARG;
+  if (!h->tracks) return SAMSIM_ERR_ARG;
+  if (track < 0 || track >= h->ntracks) return SAMSIM_ERR_ARG;
+  if (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) return SAMSIM_ERR_ARG;
+  return SAMSIM_OK;
+}
+
+int samsim_get_tracks(samsim_handle *h, int32_t track, int64_t col0, int64_t ncols, double *out) {
+  int rc = check_track_window(h, out, track, col0, ncols);
+  if (rc) return rc;
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  const size_t nc = (size_t)h->ncol, w = (size_t)ncols;
+  HIPCHK(hipMemcpy2D(out, w * sizeof(double), h->tracks + (size_t)track * SAMSIM_NTF * nc + (size_t)col0, nc * sizeof(double),
+                     w * sizeof(double), (size_t)SAMSIM_NTF, hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+int samsim_set_track_state(samsim_handle *h, int32_t track, int64_t col0, int64_t ncols, const double *in) {
+  int rc = check_track_window(h, in, track, col0, ncols);
+  if (rc) return rc;
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  const size_t nc = (size_t)h->ncol, w = (size_t)ncols;
+  HIPCHK(hipMemcpy2D(h->tracks + (size_t)track * SAMSIM_NTF * nc + (size_t)col0, nc * sizeof(double), in, w * sizeof(double),
+                     w * sizeof(double), (size_t)SAMSIM_NTF, hipMemcpyHostToDevice));
   return SAMSIM_OK;
 }
 
