@@ -210,27 +210,37 @@ template <bool WARM = false>
 __device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, double T_in, double &T_out, double &phi_out, int *evals = nullptr,
                                           double *S_br_out = nullptr) {
   const double Tl = T_liquid(H);
-  const bool mushy = S_br_clamped(s, Tl, S_bu) > S_bu && S_bu > 0.001;
+  const bool above = S_br_clamped(s, Tl, S_bu) > S_bu, salty = S_bu > 0.001;   // mushy = above && salty
   const double A0 = -latent_heat - H, LS = latent_heat * S_bu;
   const NewtonConsts nc = newton_consts(s);
   double T;
   bool more0, ok;
   newton_eval(s, nc, A0, LS, T_in, T, more0, ok);
-  // `more` and `odd` travel through the loop as 0 / 1 words in vector registers, not as lane masks: the loop test is then one compare
-  // whose result is the branch condition and the select mask of the update at once
-  int odd_i = (!mushy || !ok) ? 1 : 0;
-  int more_i = (more0 && odd_i == 0) ? 1 : 0;
+  // `more` and `odd` travel through the loop as 64-bit lane masks in scalar register pairs, one bit per lane: their bookkeeping
+  // (and / or / andn2, the loop test `more_m == 0`) issues on the scalar unit beside the vector work of the evaluation, and the
+  // select of T reads the pair as its mask directly; every vector instruction costs the SIMD four cycles, a 0 / 1 word per lane
+  // cost six per trip.  Two things this rests on, both true of every caller:
+  //  * partial exec -- a ballot only sees active lanes, and getT_chain runs under partial exec everywhere (`if (k <= Na)` in the up
+  //    sweep, the last wave of a handle whose column count is no multiple of 64, prologue_top_layer, the full first sweep): an
+  //    inactive lane's bit is 0 in every mask, so it neither keeps the loop alive nor is marked odd;
+  //  * uniform control flow -- every call site reaches the loop in wave-uniform control flow (the masks are the wave's, the branch
+  //    on `more_m == 0` is scalar), as the `ballot == 0` break of the 0 / 1-word form already required.
+  // odd_m = ballot(!mushy || !ok), as the ballot of each compare, OR-ed on the scalar side (the ballot of an OR of compares is formed
+  // through a 0 / 1 word in a vector register: a v_cndmask and a v_cmp more)
+  unsigned long long odd_m = __builtin_amdgcn_ballot_w64(!above) | __builtin_amdgcn_ballot_w64(!salty) | __builtin_amdgcn_ballot_w64(!ok);
+  unsigned long long more_m = __builtin_amdgcn_ballot_w64(more0) & ~odd_m;
   int i = 0;
   double T_fr = 0.0;
   bool have_T_fr = false;
   ISA_MARK("NEWTON_LOOP");
   for (;;) {
-    const bool more = more_i != 0;
-    if (__builtin_amdgcn_ballot_w64(more) == 0ull) break;
+    if (more_m == 0ull) break;
+    const bool more = __builtin_amdgcn_inverse_ballot_w64(more_m);
     if (WARM) {
-      const bool out = more && (T > 0.0 || T < -200.0);
-      if (wave_any(out)) {
-        if (out) {
+      // (wave_any(more && (T > 0 || T < -200)), the ballots combined on the scalar side like left_m below)
+      const unsigned long long out_m = more_m & (__builtin_amdgcn_ballot_w64(T > 0.0) | __builtin_amdgcn_ballot_w64(T < -200.0));
+      if (out_m != 0ull) {
+        if (__builtin_amdgcn_inverse_ballot_w64(out_m)) {
           if (!have_T_fr) { T_fr = T_freeze_of(s, S_bu); have_T_fr = true; }
           T = T_fr;
         }
@@ -239,16 +249,20 @@ __device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, 
     double Tn;
     bool m2, ok2;
     newton_eval(s, nc, A0, LS, T, Tn, m2, ok2);
-    const bool left = WARM ? !ok2 : (T > 0.0 || T < -200.0 || !ok2);   // (the test is on the iterate the evaluation started from)
+    // (the test is on the iterate the evaluation started from; the ballot of each compare, OR-ed on the scalar side: the ballot of
+    // their OR goes through a 0 / 1 word in a vector register)
+    unsigned long long left_m = __builtin_amdgcn_ballot_w64(!ok2);
+    if (!WARM) left_m |= __builtin_amdgcn_ballot_w64(T > 0.0) | __builtin_amdgcn_ballot_w64(T < -200.0);
+    const unsigned long long m2_m = __builtin_amdgcn_ballot_w64(m2);
 #if SAMSIM_STAMPS == 2
     if (evals && more) *evals += 1;
 #endif
     T = more ? Tn : T;
-    odd_i = left ? (odd_i | more_i) : odd_i;
-    more_i = (left || !m2) ? 0 : more_i;
-    if (++i == 260) { odd_i |= more_i; break; }       // no convergence in 260 evaluations: the general routine reports it (STOP 99)
+    odd_m |= left_m & more_m;
+    more_m &= m2_m & ~left_m;
+    if (++i == 260) { odd_m |= more_m; break; }       // no convergence in 260 evaluations: the general routine reports it (STOP 99)
   }
-  const bool odd = odd_i != 0;
+  const bool odd = __builtin_amdgcn_inverse_ballot_w64(odd_m);
   ISA_MARK("NEWTON_LOOP_END");
   double phi = S_br_out ? 0.0 : 1.0 - quot(S_bu, S_br_clamped(s, T, S_bu));
   int rc = 0;
