@@ -33,7 +33,8 @@ enum { ST_PRO = 0, ST_DFUSED, ST_DUNFUSED, ST_SURF, ST_UP, ST_POST, ST_HEAD, ST_
        CT_WAVESTEPS = 8, CT_FUSED, CT_UNFUSED, CT_UP_TRIPS, CT_NEWTON_WAVE, CT_NEWTON_LANE, CT_LANES, CT_DOWN_TRIPS, CT_DRAIN_WAVE,
        CT_DRAIN_LANE, CT_DIRTY, CT_L_COUPLING, ST_U_HEAD = 20, ST_U_GETT, ST_U_TAIL, ST_D_A, ST_D_B,
        CT_L_FLOODP = 25, CT_L_IRREG, CT_L_DIRTY, CT_L_UNFUSED, CT_L_FLUSH3, CT_L_REGRID, CT_L_FREEBOARD,
-       CT_REFILL = 32, CT_ROWS, CT_ROWS_STILL, CT_ODD_LANES, CT_ODD_WAVES, CT_ODD_EVALS_WAVE, CT_LITE, ST_NSLOT = 48 };
+       CT_REFILL = 32, CT_ROWS, CT_ROWS_STILL, CT_ODD_LANES, CT_ODD_WAVES, CT_ODD_EVALS_WAVE, CT_LITE,
+       CT_RAY_ROWS = 39, CT_RAY_ROWS_BOUND, CT_ABOVE_ROWS, CT_ABOVE_FAST, ST_NSLOT = 48 };
 struct Stamps {
   unsigned long long *acc;   // [48] in LDS, one block = one wave
   unsigned long long t0;

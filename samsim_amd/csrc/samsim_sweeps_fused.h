@@ -82,8 +82,29 @@ __device__ __forceinline__ void s1_layer(Col &c, const Ctx &x, int k, int Na, bo
       r.st = r.st + thick;
       double ray;
       const double d_S_br = S_br - r.S_br_bot;
-      if (CFG(harmonic_flag) == 2) {
-        const double hp = (r.minp < x.p14) ? 0.0 : quot(r.st + r.bot, r.stp + r.botterm);
+      const bool harmonic = CFG(harmonic_flag) == 2;
+      // numerator and divisor of the harmonic-mean permeability (formed once for the vote below and for the quotient)
+      const double h_sum = harmonic ? r.st + r.bot : 0.0, h_den = harmonic ? r.stp + r.botterm : 0.0;
+      // A sparse row is stored only when some lane's Rayleigh number exceeds ray_crit, and three rows in four hold none: the vote does
+      // not need the number.  ray = c * d_S_br * height * (st+bot) / (stp+botterm) up to a few ulp (c: the constants of the product
+      // below), so c * d_S_br * height * (st+bot) < ray_crit * (1 - 2**-20) * (stp+botterm) puts it below ray_crit with a margin
+      // that is 2**30 times the rounding error of either side; minp < p14 makes hp, and with it ray, 0.  Where that holds in every lane
+      // the quotient, the product, the store and the row flag are skipped -- what the vote on the number itself would have decided.
+      // Any other lane (a NaN operand fails P < Q like a large one) sends the whole wave through the code below, unchanged.
+      if (sparse_rows && harmonic && k != 1 && !x.ray_rows_all) {
+        // (the product's last constant 1 / (kappa_l * mu) stands on Q's side, so that P begins with the two products the number
+        // itself begins with: a row that is not decided has paid two multiplications and a compare for the attempt)
+        constexpr double q_ray = ray_crit * (1.0 - 0x1p-20) * (kappa_l * mu);
+        const double P = grav_f * rho_l * bbeta * d_S_br * height * h_sum, Q = q_ray * h_den;
+        ST_COUNT(CT_RAY_ROWS, 1);
+        // (the ballot of each compare, AND-ed on the scalar side: a lane is undecided when neither test puts it below)
+        if ((__builtin_amdgcn_ballot_w64(!(P < Q)) & __builtin_amdgcn_ballot_w64(!(r.minp < x.p14))) == 0ull) {
+          ST_COUNT(CT_RAY_ROWS_BOUND, 1);
+          return;
+        }
+      }
+      if (harmonic) {
+        const double hp = (r.minp < x.p14) ? 0.0 : quot(h_sum, h_den);
         ray = grav_f * rho_l * bbeta * d_S_br * height * hp;
       } else {
         ray = grav_f * rho_l * bbeta * d_S_br * height * dmin(r.minp, r.perm_bot);
@@ -667,6 +688,9 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
   // a wave the same for one column as for 64) -- it then only runs the second getT chain, and says so for all its columns
   // (COLF_DIRTY: the full first sweep gives a column the same bits as the fused one).  A wave that does not flush after all has lost
   // nothing but the fused first sweep of one step.
+  // (NewtonConsts: three constants of getT's evaluation as vector values, formed where a stretch of layers begins -- six v_mov_b32
+  // per sweep and stretch instead of per layer -- and carried through the trip loop)
+  NewtonConsts nc_s = newton_consts(s);   // (a wave with a hand-made column keeps this one for the whole sweep)
   auto body = [&](const int k, const UL &row, const double th_k, const double rth_k, auto top_tag, auto lite_tag) {
     constexpr bool TOP = decltype(top_tag)::value;
     constexpr bool LITE = decltype(lite_tag)::value;
@@ -700,8 +724,10 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
     ST_MARK(ST_U_HEAD);
 #if SAMSIM_STAMPS == 2
     int evals = 1;
-    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi, &evals) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi, &evals, LITE ? nullptr : &S_br_T);
+    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi, &evals) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi, &evals, LITE ? nullptr : &S_br_T, &nc_s);
     {
+      if (!TOP) { ST_COUNT(CT_ABOVE_ROWS, 1); if (__ballot(evals < 0)) ST_COUNT(CT_ABOVE_FAST, 1); }   // (bit 31: the wave-level shortcut of getT_chain decided `above`)
+      evals &= 0x7fffffff;
       const bool was_odd = (evals >> 30) & 1;
       const int redo = (evals >> 16) & 0x3fff;
       evals &= 0xffff;
@@ -713,7 +739,7 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
     { int tot = 0; unsigned long long mk = __ballot(1); while (mk) { const int ln = __ffsll((long long)mk) - 1; tot += __builtin_amdgcn_readlane(evals, ln); mk &= mk - 1; }
       ST_COUNT(CT_NEWTON_LANE, (unsigned long long)tot); }
 #else
-    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi, nullptr, LITE ? nullptr : &S_br_T);
+    int rr = TOP ? getT(s, H, S_bu, T_test, T, phi) : getT_chain<LITE>(s, H, S_bu, T_test, T, phi, nullptr, LITE ? nullptr : &S_br_T, &nc_s);
 #endif
     if (!TOP) { ISA_MARK("U_GETT_END"); }
     ST_MARK(ST_U_GETT);
@@ -756,6 +782,7 @@ __device__ __forceinline__ void sweep_up_fused(Col &c, const Ctx &x, long long c
       const int klo = stretch == 0 ? b1 + 1 : (stretch == 1 ? b0 + 1 : 2);
       // (formed where the stretch begins -- the elastic block's thickness is one load per sweep -- so that only this pair is carried)
       const double th_s = stretch == 1 ? LAYU(SAMSIM_A_THICK, g.n_top + 1) : g.thick_0, rth_s = recip(th_s);
+      nc_s = newton_consts(s);
       for (; k - 2 >= klo; k -= 3) {
         ISA_MARK("U_ITER_BEGIN");
         ST_MARK(ST_UP);

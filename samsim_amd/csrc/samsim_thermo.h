@@ -206,13 +206,25 @@ __device__ __forceinline__ int getT(const Salt &s, double H, double S_bu, double
 // S_br_out (the fused up sweep's full layers): the clamped liquidus salinity at the temperature returned, which the first sweep of the
 // next step needs as well, is formed ONCE, after the redo, and handed out: a lane that was not redone keeps the loop's temperature, so
 // its phi comes from the same operands as before, and the polynomial is not evaluated a second time behind the redo.
+// The pure-brine test `above` (the liquidus salinity at H/c_l exceeds S_bu) holds for every layer that has ice in it, and only its
+// wave-level vote is used.  Both liquidus cubics fall strictly with T (the derivative has no real root: 1.038**2 < 4*0.01605*18.7,
+// 0.778**2 < 4*0.01086*17.6) and are 51.6 and 49.4 at -3 C: where every active lane has H/c_l < -3 and S_bu < 40 the test holds in
+// all of them -- nine units of margin against a rounding error of 1e-14 -- and the cubic is not evaluated.  A NaN fails either
+// compare and takes the evaluation.
+// nc_in: NewtonConsts the caller formed (the fused up sweep: once per stretch of layers instead of once per layer).
 template <bool WARM = false>
 __device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, double T_in, double &T_out, double &phi_out, int *evals = nullptr,
-                                          double *S_br_out = nullptr) {
+                                          double *S_br_out = nullptr, const NewtonConsts *nc_in = nullptr) {
   const double Tl = T_liquid(H);
-  const bool above = S_br_clamped(s, Tl, S_bu) > S_bu, salty = S_bu > 0.001;   // mushy = above && salty
+  const bool salty = S_bu > 0.001;   // mushy = above && salty
   const double A0 = -latent_heat - H, LS = latent_heat * S_bu;
-  const NewtonConsts nc = newton_consts(s);
+  const NewtonConsts nc = nc_in ? *nc_in : newton_consts(s);
+  const bool short_cut = (__builtin_amdgcn_ballot_w64(!(Tl < -3.0)) | __builtin_amdgcn_ballot_w64(!(S_bu < 40.0))) == 0ull;
+  unsigned long long brine_m = 0ull;   // ballot(!above)
+  if (!short_cut) brine_m = __builtin_amdgcn_ballot_w64(!(S_br_clamped(s, Tl, S_bu) > S_bu));
+#if SAMSIM_STAMPS == 2
+  if (short_cut && evals) *evals = (int)((unsigned)*evals | 0x80000000u);   // (decoded by the caller: CT_ABOVE_FAST)
+#endif
   double T;
   bool more0, ok;
   newton_eval(s, nc, A0, LS, T_in, T, more0, ok);
@@ -227,7 +239,7 @@ __device__ __forceinline__ int getT_chain(const Salt &s, double H, double S_bu, 
   //    on `more_m == 0` is scalar), as the `ballot == 0` break of the 0 / 1-word form already required.
   // odd_m = ballot(!mushy || !ok), as the ballot of each compare, OR-ed on the scalar side (the ballot of an OR of compares is formed
   // through a 0 / 1 word in a vector register: a v_cndmask and a v_cmp more)
-  unsigned long long odd_m = __builtin_amdgcn_ballot_w64(!above) | __builtin_amdgcn_ballot_w64(!salty) | __builtin_amdgcn_ballot_w64(!ok);
+  unsigned long long odd_m = brine_m | __builtin_amdgcn_ballot_w64(!salty) | __builtin_amdgcn_ballot_w64(!ok);
   unsigned long long more_m = __builtin_amdgcn_ballot_w64(more0) & ~odd_m;
   int i = 0;
   double T_fr = 0.0;

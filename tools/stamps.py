@@ -21,7 +21,10 @@ NAMES = ["t_prologue", "t_down_fused", "t_down_unfused", "t_surface", "t_up", "t
          "drain_lane", "dirty", "lanes_coupling", "t_up_head", "t_up_getT", "t_up_tail", "t_down_A", "t_down_BC",
          "lanes_flood_possible", "lanes_irregular", "lanes_dirty", "lanes_unfused", "lanes_flush3", "lanes_regrid", "lanes_freeboard",
          "lanes_refill_psi", "down_rows_interior", "down_rows_without_expulsion", "getT_lanes_redone_by_the_general_routine",
-         "getT_waves_with_such_a_lane", "their_evaluations_wave_max", "up_sweeps_without_the_next_first_sweep"] + [f"slot{i}" for i in range(39, 48)]
+         "getT_waves_with_such_a_lane", "their_evaluations_wave_max", "up_sweeps_without_the_next_first_sweep",
+         # the wave-level votes of the fused up sweep: sparse Rayleigh rows seen / decided by the division-free bound; getT_chain
+         # layer rows / those whose pure-brine test the shortcut decided
+         "ray_rows", "ray_rows_bound", "getT_rows", "getT_rows_above_by_shortcut"] + [f"slot{i}" for i in range(43, 48)]
 
 
 def main():
