@@ -93,6 +93,18 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: threshold
   END TYPE samsim_track_spec
 
+  ! samsim_select_columns / samsim_get_columns: enum samsim_select_status, one term (holds when lo <= x < hi) and the selection
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_SELECT_RUNNING = 0, SAMSIM_SELECT_STOPPED = 1, SAMSIM_SELECT_CODE = 2, SAMSIM_SELECT_ANY = 3
+  INTEGER, PARAMETER :: SAMSIM_SELECT_MAX_TERMS = 4, SAMSIM_SELECT_MAX_OUT = 262144
+  TYPE, BIND(C) :: samsim_select_term
+     INTEGER(c_int32_t) :: slot, reserved                        ! slot 0-based, -1 = N_active, or samsim_track_slot
+     REAL(c_double)     :: lo, hi
+  END TYPE samsim_select_term
+  TYPE, BIND(C) :: samsim_selection
+     INTEGER(c_int32_t) :: struct_size, nterms, group, status_mode, code, reserved
+     TYPE(samsim_select_term) :: terms(SAMSIM_SELECT_MAX_TERMS)
+  END TYPE samsim_selection
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -312,6 +324,26 @@ MODULE mo_samsim_capi
        INTEGER(c_int32_t), VALUE :: track
        INTEGER(c_int64_t), VALUE :: col0, ncols
        REAL(c_double), INTENT(in) :: in(*)
+     END FUNCTION
+     !> the 0-based indices of the columns a selection holds for, ascending: cols_out(max_out) receives the first min(n_match, max_out),
+     !! n_match the exact number of matches
+     INTEGER(c_int) FUNCTION samsim_select_columns(h, sel, max_out, cols_out, n_match) BIND(C, name='samsim_select_columns')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(samsim_selection), INTENT(in) :: sel
+       INTEGER(c_int64_t), VALUE :: max_out
+       INTEGER(c_int64_t), INTENT(out) :: cols_out(*)
+       INTEGER(c_int64_t), INTENT(out) :: n_match
+     END FUNCTION
+     !> the state of the columns cols(1:ncols) (0-based indices, any order), position j holding column cols(j); s%ncol = ncols;
+     !! status, step, layer: c_loc of arrays of ncols entries, or c_null_ptr
+     INTEGER(c_int) FUNCTION samsim_get_columns(h, ncols, cols, s, status, step, layer) BIND(C, name='samsim_get_columns')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: ncols
+       INTEGER(c_int64_t), INTENT(in) :: cols(*)
+       TYPE(samsim_state_soa), INTENT(inout) :: s
+       TYPE(c_ptr), VALUE :: status, step, layer
      END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')

@@ -5,7 +5,8 @@
 !!
 !! New surface the reference does not have (SURVEY.md, introduction): a namelist file `samsim.nml`
 !!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites,
-!!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every /
+!!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every, members_thinner,
+!!                 members_max /
 !! (col0 / ncol_total: this process owns the global columns col0 .. col0+ncol-1 of an ensemble of ncol_total -- one host
 !! process per GPU, contiguous column ranges, no exchange between them, SURVEY.md section 8e)
 !!   &samsim_flags <any flag of mo_data.f90:136-155 or scalar set by mo_init> /       (overrides init(testcase))
@@ -40,6 +41,8 @@ MODULE mo_data
   REAL(wp)            :: hist_max = 0._wp    !< upper edge of the last bin [m]: edges j*hist_max/hist_bins, j = 0..hist_bins
   LOGICAL             :: sens = .FALSE.      !< sensitivities to the perturbation at every output point: slopes and correlations on dT2m and precip_scale (dat_ens_sens.dat, dat_ens_sens_profile_*.dat)
   INTEGER(c_int64_t)  :: track_every = 0     !< > 0: time-domain diagnostics, sampled on the device after every track_every-th step: the ice thickness, and the surface temperature with the condition T_top >= 0 (dat_ens_track.dat at the end of the run)
+  REAL(wp)            :: members_thinner = 0._wp   !< > 0 [m]: at the end of the run the members whose ice (the thickness slot) is thinner than this, selected on the device: their indices and scalars (dat_ens_members.dat) and their profiles (dat_ens_members_{T,S_bu,thick}.dat)
+  INTEGER             :: members_max = 64    !< at most this many members are written, the first in column order
   LOGICAL             :: by_site = .FALSE.   !< stats_by_site asked for and the run has more than one site: the handle carries the sites as group labels
   INTEGER             :: i_time, i_time_out
   REAL(wp)            :: fl_q_bottom = 0._wp, T_top = 0._wp, fl_sw = 0._wp, fl_rest = 0._wp, T2m = 0._wp, tank_depth = 0._wp
@@ -658,6 +661,55 @@ CONTAINS
     CLOSE(62)
   END SUBROUTINE output_tracks
 
+  !> Written once at the end of a run with members_thinner > 0: the running members whose thickness slot lies below members_thinner,
+  !! the first members_max of them in column order, selected on the device (samsim_select_columns) and fetched in one call
+  !! (samsim_get_columns).  dat_ens_members.dat: one row per member -- the 0-based column index (of this process), N_active, thickness,
+  !! thick_snow, T_top.  dat_ens_members_{T,S_bu,thick}.dat: one row per member with the Nlayer values of the array.
+  SUBROUTINE output_members(h)
+    USE, INTRINSIC :: ieee_arithmetic, ONLY: ieee_value, ieee_negative_inf
+    TYPE(c_ptr), INTENT(in) :: h
+    TYPE(samsim_selection) :: sel
+    TYPE(samsim_state_soa) :: ms
+    INTEGER(c_int64_t), ALLOCATABLE :: cols(:)
+    REAL(c_double), ALLOCATABLE, TARGET :: mlay(:, :, :), mscal(:, :)
+    INTEGER(c_int32_t), ALLOCATABLE, TARGET :: mna(:)
+    INTEGER(c_int64_t) :: n_match, n
+    INTEGER :: j, k, a, nl
+    INTEGER, PARAMETER :: arrays(3) = (/ A_T, A_S_BU, A_THICK /)
+    CHARACTER(len=64) :: fmt
+    IF (.NOT. members_thinner > 0._wp) RETURN
+    sel%struct_size = INT(c_sizeof(sel), c_int32_t)
+    sel%nterms = 1; sel%group = -1; sel%status_mode = SAMSIM_SELECT_RUNNING; sel%code = 0; sel%reserved = 0
+    sel%terms%slot = 0; sel%terms%reserved = 0; sel%terms%lo = 0._wp; sel%terms%hi = 0._wp
+    sel%terms(1)%slot = INT(S_THICKNESS - 1, c_int32_t)
+    sel%terms(1)%lo = ieee_value(1._wp, ieee_negative_inf)
+    sel%terms(1)%hi = members_thinner
+    ALLOCATE(cols(members_max))
+    CALL samsim_check(samsim_select_columns(h, sel, INT(members_max, c_int64_t), cols, n_match), 'samsim_select_columns')
+    n = MIN(n_match, INT(members_max, c_int64_t))
+    nl = INT(cfg%nlayer)
+    OPEN(63, file='./output/dat_ens_members.dat',       STATUS='replace', Recl=256)
+    OPEN(64, file='./output/dat_ens_members_T.dat',     STATUS='replace', Recl=64 + 16*nl)
+    OPEN(65, file='./output/dat_ens_members_S_bu.dat',  STATUS='replace', Recl=64 + 16*nl)
+    OPEN(66, file='./output/dat_ens_members_thick.dat', STATUS='replace', Recl=64 + 16*nl)
+    IF (n > 0) THEN
+       ALLOCATE(mlay(n, nl, SAMSIM_NARR), mscal(n, SAMSIM_NSCAL), mna(n))
+       ms%ncol = n; ms%nlayer = cfg%nlayer; ms%narr = INT(SAMSIM_NARR, c_int32_t)
+       ms%lay = c_loc(mlay); ms%scal = c_loc(mscal); ms%n_active = c_loc(mna)
+       CALL samsim_check(samsim_get_columns(h, n, cols, ms, c_null_ptr, c_null_ptr, c_null_ptr), 'samsim_get_columns')
+       WRITE(fmt, '(A,I0,A)') '(', nl, 'ES16.8)'
+       DO j = 1, INT(n)
+          WRITE(63, '(I12,I6,3ES16.8)') cols(j), mna(j), mscal(j, S_THICKNESS), mscal(j, S_THICK_SNOW), mscal(j, S_T_TOP)
+          DO a = 1, 3
+             WRITE(63 + a, fmt) (mlay(j, k, arrays(a)), k = 1, nl)
+          END DO
+       END DO
+       DEALLOCATE(mlay, mscal, mna)
+    END IF
+    CLOSE(63); CLOSE(64); CLOSE(65); CLOSE(66)
+    DEALLOCATE(cols)
+  END SUBROUTINE output_members
+
   !> the units of dat_ens_profile_{T,S_bu,psi_l}_site<kk>.dat: array a = 1..3 of site s = 1..nsites.  nsites is at most
   !! SIZE(sites) = 16 (the namelist holds no more directories), so the units stay within 601..648 and <kk> within two digits.
   INTEGER FUNCTION site_unit(a, s)
@@ -998,6 +1050,7 @@ CONTAINS
          ' column-timesteps/s)'
     IF (LEN_TRIM(restart_out) > 0) CALL write_restart(h, restart_out)
     CALL output_tracks(h)
+    CALL output_members(h)
     CALL output_end()
     CALL samsim_destroy(h)
     CALL sub_deallocate()
@@ -1013,7 +1066,8 @@ PROGRAM SAMSIM
   CHARACTER*12000 :: description
   LOGICAL         :: have_nml
   NAMELIST /samsim_run/ testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, &
-       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every
+       restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every, &
+       members_thinner, members_max
 
   testcase    = 1
   description = 'MI355X-native batched column solver'
@@ -1029,6 +1083,10 @@ PROGRAM SAMSIM
      END IF
      IF (hist_bins < 0 .OR. hist_bins > SAMSIM_HIST_MAX_VBINS .OR. (hist_bins > 0 .AND. .NOT. hist_max > 0._wp)) THEN
         PRINT *, 'samsim_run: hist_bins must lie in 0 ..', SAMSIM_HIST_MAX_VBINS, ' and hist_max must be > 0'
+        STOP 4
+     END IF
+     IF (.NOT. members_thinner >= 0._wp .OR. members_max < 1 .OR. members_max > SAMSIM_SELECT_MAX_OUT) THEN
+        PRINT *, 'samsim_run: members_thinner must be >= 0 and members_max must lie in 1 ..', SAMSIM_SELECT_MAX_OUT
         STOP 4
      END IF
   END IF

@@ -513,6 +513,72 @@ int samsim_get_tracks(samsim_handle *h, int32_t track, int64_t col0, int64_t nco
 int samsim_set_track_state(samsim_handle *h, int32_t track, int64_t col0, int64_t ncols, const double *in /*[SAMSIM_NTF][ncols]*/);
 #define SAMSIM_TRACK_SLOT(track, field) (0x10000 + (track) * 32 + (field))
 
+/* Which columns, and what they look like.  Every reduction above answers a question about the ensemble as a whole; a histogram that
+ * says 412 members are thinner than 0.3 m, or a status that says three columns stopped, ends in "show me those columns".  The two
+ * entry points below return the indices of the columns a predicate holds for, evaluated on the device, and the full state of an
+ * arbitrary list of columns -- without a download of the whole state and without one samsim_get_state per column.  They return
+ * indices and the state of existing columns and write nothing to the ensemble: this is neither exact selection of quantiles nor a copy
+ * of columns.  They were added without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only, found by symbol as the group,
+ * histogram, sensitivity and track functions are.
+ *
+ *   samsim_select_columns.  A column matches when its status passes status_mode, its label passes group and every term holds.
+ *     Slots.  A slot is an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE (x is then (double)n_active) or SAMSIM_TRACK_SLOT(track, field) of
+ *       the tracks in force: what every reduction above accepts.
+ *     Terms.  A term holds when lo <= x && x < hi, two IEEE comparisons: a NaN x satisfies no term; lo = -inf and hi = +inf are
+ *       allowed; lo >= hi is allowed and gives an empty selection.  The terms are ANDed; nterms == 0 puts no condition on values.
+ *     Status.  SAMSIM_SELECT_RUNNING: status == 0, the columns the statistics count.  SAMSIM_SELECT_STOPPED: status != 0.
+ *       SAMSIM_SELECT_CODE: status == code.  SAMSIM_SELECT_ANY: every column.  A stopped column is tested on the values it froze with.
+ *     Group.  -1: any column, no labels needed.  >= 0: only the columns with that label (samsim_set_groups).
+ *     Result.  *n_match is the exact number of matching columns, whatever max_out is.  cols_out receives the first
+ *       min(*n_match, max_out) matching column indices in ascending order; entries beyond them are left alone.  max_out == 0 with
+ *       cols_out == NULL only counts.  With the status mode RUNNING the matches of the term [E_j, E_{j+1}) are entry j+1 of
+ *       samsim_get_histogram, and with no terms *n_match is the count of samsim_get_ensemble_stats (samsim_get_group_stats with a group).
+ *     Invariants.  The order is fixed and the counts are integers; no atomics, no hand-off between workgroups: two calls on the same
+ *       state return the same bytes.  Relabelling columns outside `group` does not change the result.  Like every getter the call waits
+ *       for the handle's streams; it changes neither the state, the status, the clock, the labels, the tracks nor the output snapshot.
+ *     Errors, all found before any device work, in this order.  SAMSIM_ERR_ARG: h, sel or n_match NULL.  SAMSIM_ERR_ABI: wrong
+ *       struct_size.  SAMSIM_ERR_ARG: nterms out of range; per term in order a bad slot, reserved != 0, a NaN lo or hi; group < -1,
+ *       group >= 0 without labels, or group >= ngroups; a status_mode outside the enum, or a non-zero code where the mode takes none;
+ *       reserved != 0; max_out < 0, max_out > SAMSIM_SELECT_MAX_OUT, or max_out > 0 with cols_out NULL.
+ *   samsim_get_columns.  The state of the columns cols[0 .. ncols), in the boundary's layout.
+ *     Request.  s->ncol == ncols in 1..SAMSIM_SELECT_MAX_OUT, s->nlayer the handle's, s->narr SAMSIM_NPROG or SAMSIM_NARR.  Every cols[j]
+ *       lies in [0, ncol); the whole list is checked on the host before any device work.  Any order is allowed, and so are duplicates.
+ *     Result.  Position j of lay [narr][nlayer][ncols], scal [SAMSIM_NSCAL][ncols] and n_active [ncols] holds column cols[j]: exactly the
+ *       bytes samsim_get_state returns for a one-column window at cols[j], the clamp S_abs >= 0 and the refreshed S_bu = S_abs/m
+ *       included, under that function's conditions (after a step; status 0; the active layers; the clamp not in a column uploaded
+ *       since the last step; the quotient where m != 0).  status, step and layer are [ncols] each or NULL and receive the entries
+ *       samsim_get_status returns for those columns.
+ *     No writes to the ensemble.  Clamp and quotient are formed in registers, as the track sampler forms them, so a column listed
+ *       twice races with nothing; a later samsim_get_state still returns the same bytes, because it applies the same clamp.
+ *     Staging.  The layer arrays pass through the staging buffer of samsim_get_state, in pieces of at most SAMSIM_STAGE_MAX_BYTES cut
+ *       by the same rule (whole multiples of 64 list positions): at 1 024 layers SAMSIM_SELECT_MAX_OUT columns are far more than one piece.
+ *     Errors, all found before any device work.  SAMSIM_ERR_ARG: h, cols or s NULL; the shape checks of samsim_get_state (a NULL array,
+ *       a wrong nlayer or narr); ncols out of range or s->ncol != ncols; an index out of range.  Nothing is written to the caller's
+ *       buffers when a call is refused.
+ *     Tracers.  The tracer state is not part of this call: it stays with samsim_get_tracer_state.
+ *   Device scratch of both calls: at most SAMSIM_SELECT_SCRATCH_BYTES whatever ncol and the request are (the waves' counts and
+ *     offsets, and the index list); allocated on first use, kept in the handle, freed by samsim_destroy. */
+#define SAMSIM_SELECT_MAX_TERMS 4
+#define SAMSIM_SELECT_MAX_OUT   262144            /* indices per call, and columns per samsim_get_columns */
+#define SAMSIM_SELECT_SCRATCH_BYTES (4ull << 20)  /* device scratch of both calls, whatever ncol and the request are */
+enum samsim_select_status { SAMSIM_SELECT_RUNNING = 0,   /* status == 0: the columns the statistics count */
+                            SAMSIM_SELECT_STOPPED,       /* status != 0 */
+                            SAMSIM_SELECT_CODE,          /* status == code */
+                            SAMSIM_SELECT_ANY };
+typedef struct samsim_select_term { int32_t slot, reserved; double lo, hi; } samsim_select_term;   /* holds when lo <= x && x < hi */
+typedef struct samsim_selection {
+  int32_t struct_size;      /* = sizeof(samsim_selection) */
+  int32_t nterms;           /* 0..SAMSIM_SELECT_MAX_TERMS; the terms are ANDed; 0 = no condition on values */
+  int32_t group;            /* -1: any column; >= 0: only columns with that label (samsim_set_groups) */
+  int32_t status_mode;      /* enum samsim_select_status */
+  int32_t code;             /* SAMSIM_SELECT_CODE only, else 0 */
+  int32_t reserved;         /* 0 */
+  samsim_select_term terms[SAMSIM_SELECT_MAX_TERMS];
+} samsim_selection;
+int samsim_select_columns(samsim_handle *h, const samsim_selection *sel, int64_t max_out, int64_t *cols_out, int64_t *n_match);
+int samsim_get_columns(samsim_handle *h, int64_t ncols, const int64_t *cols, samsim_state_soa *s,
+                       int32_t *status, int64_t *step, int32_t *layer);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

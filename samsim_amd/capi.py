@@ -177,6 +177,40 @@ def _slot(name) -> int:
     return -1 if name == "N_active" else S[name]
 
 
+SELECT_MAX_TERMS = 4        # SAMSIM_SELECT_MAX_TERMS
+SELECT_MAX_OUT = 262144     # SAMSIM_SELECT_MAX_OUT: indices per select, and columns per get_columns
+# enum samsim_select_status
+SELECT_STATUS = {"running": 0, "stopped": 1, "code": 2, "any": 3}
+
+
+class SelectTerm(C.Structure):
+    """samsim_select_term: holds when lo <= x && x < hi for the column's value x of the slot"""
+    _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class Selection(C.Structure):
+    """samsim_selection: the ANDed terms, the label and the status mode a column must pass"""
+    _fields_ = [("struct_size", C.c_int32), ("nterms", C.c_int32), ("group", C.c_int32), ("status_mode", C.c_int32),
+                ("code", C.c_int32), ("reserved", C.c_int32), ("terms", SelectTerm * SELECT_MAX_TERMS)]
+
+    @staticmethod
+    def make(terms=(), group=None, status="running") -> "Selection":
+        """terms: (name_or_slot, lo, hi) with names from SCALARS, "N_active", or ints of track_slot; status "running", "stopped",
+        "any" or an integer STOP code"""
+        sel = Selection()
+        sel.struct_size = C.sizeof(Selection)
+        terms = list(terms)
+        sel.nterms = len(terms)
+        for i, (name, lo, hi) in enumerate(terms[:SELECT_MAX_TERMS]):
+            sel.terms[i] = SelectTerm(_slot(name), 0, float(lo), float(hi))
+        sel.group = -1 if group is None else int(group)
+        if isinstance(status, str):
+            sel.status_mode, sel.code = SELECT_STATUS[status], 0
+        else:
+            sel.status_mode, sel.code = SELECT_STATUS["code"], int(status)
+        return sel
+
+
 STAT_DTYPE = np.dtype([("count", np.int64), ("mean", np.float64), ("min", np.float64), ("max", np.float64), ("std", np.float64)])
 
 
@@ -376,6 +410,13 @@ class Solver:
         track_sig = {"set_tracks": [vp, C.c_int32, C.POINTER(TrackSpec), i64], "reset_tracks": [vp],
                      "get_tracks": [vp, C.c_int32, i64, i64, C.c_void_p], "set_track_state": [vp, C.c_int32, i64, i64, C.c_void_p]}
         for n, a in track_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the selection of columns and the gather of scattered ones
+        select_sig = {"select_columns": [vp, C.POINTER(Selection), i64, C.c_void_p, C.POINTER(C.c_int64)],
+                      "get_columns": [vp, i64, C.c_void_p, C.POINTER(StateSoA), C.c_void_p, C.c_void_p, C.c_void_p]}
+        for n, a in select_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -704,6 +745,44 @@ class Solver:
         set_tracks comes first"""
         buf = np.ascontiguousarray(np.stack([np.asarray(fields[f], dtype=np.float64) for f in TRACK_FIELDS]))
         self._chk(self._f("set_track_state")(self._h, int(track), col0, buf.shape[1], buf.ctypes.data), "set_track_state")
+
+    # -- which columns, and what they look like
+    def select_raw(self, sel: Selection, max_out, out=None):
+        """samsim_select_columns with the arguments as given (no checks on this side): (int64 array of the first min(n_match,
+        max_out) matching column indices in ascending order, n_match).  max_out == 0 only counts (cols_out NULL).  out: an int64
+        array of at least max_out entries to receive the indices in place (entries beyond them are left alone)"""
+        n = C.c_int64(-1)
+        if out is None:
+            out = np.zeros(max(0, min(int(max_out), SELECT_MAX_OUT)), dtype=np.int64)
+        assert out.dtype == np.int64 and out.flags.c_contiguous
+        self._chk(self._f("select_columns")(self._h, C.byref(sel), int(max_out), out.ctypes.data if int(max_out) != 0 else None,
+                                            C.byref(n)), "select_columns")
+        return out[:max(0, min(int(n.value), int(max_out)))], int(n.value)
+
+    def select(self, terms=(), group=None, status="running", max_out=SELECT_MAX_OUT):
+        """(indices, n_match): the columns for which every term (name_or_slot, lo, hi) holds -- lo <= x < hi, names from SCALARS,
+        "N_active" or ints of track_slot --, with label `group` of set_groups (None: any) and status "running" (the columns the
+        statistics count), "stopped", "any" or an integer STOP code (samsim_select_columns).  indices: int64, ascending, the first
+        min(n_match, max_out); n_match is exact whatever max_out is"""
+        return self.select_raw(Selection.make(terms, group, status), max_out)
+
+    def get_columns(self, cols, narr: int = NARR, with_status=False):
+        """State of the columns `cols` (any order, duplicates allowed, at most SELECT_MAX_OUT), position j holding column cols[j]:
+        the bytes get_state returns for those columns (samsim_get_columns).  with_status: (State, (status, step, layer)), the
+        entries of get_status for those columns"""
+        cols = np.ascontiguousarray(cols, dtype=np.int64)
+        assert cols.ndim == 1
+        n = cols.size
+        st = State.empty(max(1, n), self.nlayer, narr)
+        s = st._c()
+        s.ncol = n
+        if not with_status:
+            self._chk(self._f("get_columns")(self._h, n, cols.ctypes.data, C.byref(s), None, None, None), "get_columns")
+            return st
+        status, step, layer = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int64), np.zeros(max(1, n), dtype=np.int32)
+        self._chk(self._f("get_columns")(self._h, n, cols.ctypes.data, C.byref(s), status.ctypes.data, step.ctypes.data, layer.ctypes.data),
+                  "get_columns")
+        return st, (status, step, layer)
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

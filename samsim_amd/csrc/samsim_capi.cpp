@@ -17,6 +17,7 @@
 #include "samsim_device.h"
 #include "samsim_groups.h"
 #include "samsim_hist.h"
+#include "samsim_select.h"
 #include "samsim_sens.h"
 #include "samsim_tracks.h"
 
@@ -74,6 +75,7 @@ struct samsim_handle {
   void *d_group = nullptr;     // samsim_get_group_stats: the waves' partials of one slot, then its results (kGroupScratch bytes)
   void *d_hist = nullptr;      // samsim_get_histogram / samsim_get_profile_histogram: the 64-bit counts of one request (kHistScratch bytes)
   void *d_sens = nullptr;      // samsim_get_covariance / samsim_get_profile_regression: the waves' partials of one pass, then the results (kSensScratch bytes)
+  void *d_select = nullptr;    // samsim_select_columns / samsim_get_columns: the waves' counts and offsets, and the index list (kSelectScratch bytes)
   double *tracks = nullptr;    // [ntracks][SAMSIM_NTF][ncol] rows of the time-domain diagnostics (samsim_set_tracks), sampled by launch()
   int32_t ntracks = 0;         // 0: no tracking
   long long track_every = 0;   // a sample follows the step that brings clk.step to a multiple of it
@@ -228,6 +230,12 @@ static_assert(sizeof(uint32_t) * DEV_HIST_LDS_COUNTS <= DEV_HIST_LDS_BYTES, "a w
 constexpr size_t kSensScratch = DEV_SENS_PART_BYTES + DEV_SENS_RESULT_BYTES;
 static_assert(kSensScratch <= SAMSIM_SENS_SCRATCH_BYTES && SAMSIM_SENS_SCRATCH_BYTES <= (16ull << 20), "sensitivity scratch bound of samsim.h");
 static_assert(sizeof(samsim_pair_stat) == 48, "samsim_pair_stat of samsim.h");
+
+// device scratch of the selection and of the gather of scattered columns: the waves' counts and offsets, and the index list
+constexpr size_t kSelectScratch = DEV_SEL_BYTES;
+static_assert(kSelectScratch <= SAMSIM_SELECT_SCRATCH_BYTES && SAMSIM_SELECT_SCRATCH_BYTES <= (16ull << 20), "select scratch bound of samsim.h");
+static_assert(sizeof(samsim_select_term) == 24 && sizeof(samsim_selection) == 24 + 24 * SAMSIM_SELECT_MAX_TERMS, "samsim_selection of samsim.h");
+static_assert((size_t)SAMSIM_SELECT_MAX_OUT * DEV_SEL_COLUMN_BYTES <= kStageBytes, "the per-column rows of the largest request are one piece");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -538,6 +546,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->err_layer); (void)hipFree(h->err_step); (void)hipFree(h->work);
   (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
   (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens); (void)hipFree(h->tracks);
+  (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
   (void)hipFree(h->ocean_dflq); (void)hipFree(h->ocean_sbu);
@@ -1292,6 +1301,93 @@ int samsim_set_track_state(samsim_handle *h, int32_t track, int64_t col0, int64_
   const size_t nc = (size_t)h->ncol, w = (size_t)ncols;
   HIPCHK(hipMemcpy2D(h->tracks + (size_t)track * SAMSIM_NTF * nc + (size_t)col0, nc * sizeof(double), in, w * sizeof(double),
                      w * sizeof(double), (size_t)SAMSIM_NTF, hipMemcpyHostToDevice));
+  return SAMSIM_OK;
+}
+
+int samsim_select_columns(samsim_handle *h, const samsim_selection *sel, int64_t max_out, int64_t *cols_out, int64_t *n_match) {
+  // every check first, in the order samsim.h gives: nothing below touches the device before the request is known to be good
+  if (!h || !sel || !n_match) return SAMSIM_ERR_ARG;
+  if (sel->struct_size != (int32_t)sizeof(samsim_selection)) return SAMSIM_ERR_ABI;
+  if (sel->nterms < 0 || sel->nterms > SAMSIM_SELECT_MAX_TERMS) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < sel->nterms; ++i) {
+    const samsim_select_term &t = sel->terms[i];
+    if (!good_slot(h, t.slot)) return SAMSIM_ERR_ARG;
+    if (t.reserved != 0) return SAMSIM_ERR_ARG;
+    if (std::isnan(t.lo) || std::isnan(t.hi)) return SAMSIM_ERR_ARG;
+  }
+  if (!good_group(h, sel->group)) return SAMSIM_ERR_ARG;
+  if (sel->status_mode < SAMSIM_SELECT_RUNNING || sel->status_mode > SAMSIM_SELECT_ANY) return SAMSIM_ERR_ARG;
+  if (sel->status_mode != SAMSIM_SELECT_CODE && sel->code != 0) return SAMSIM_ERR_ARG;
+  if (sel->reserved != 0) return SAMSIM_ERR_ARG;
+  if (max_out < 0 || max_out > SAMSIM_SELECT_MAX_OUT || (max_out > 0 && !cols_out)) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
+  SelParams p{};
+  for (int i = 0; i < sel->nterms; ++i) p.t[i] = SelTerm{slot_row(h, sel->terms[i].slot), sel->terms[i].lo, sel->terms[i].hi};
+  p.n_active = h->n_active;
+  p.status = sel->status_mode == SAMSIM_SELECT_ANY ? nullptr : h->status;
+  p.labels = sel->group >= 0 ? h->groups : nullptr;
+  p.ncol = h->ncol;
+  // wave w owns the blocks [w * per, (w + 1) * per): as many waves as that leaves with a block, DEV_SEL_GRID at most
+  const long long nblk = (h->ncol + 63) / 64;
+  p.per = (nblk + DEV_SEL_GRID - 1) / DEV_SEL_GRID;
+  p.nwaves = (int32_t)((nblk + p.per - 1) / p.per);
+  p.max_out = max_out;
+  p.nterms = sel->nterms; p.group = sel->group; p.status_mode = sel->status_mode; p.code = sel->code;
+  HIPCHK(samsim_launch_select(&p, h->d_select, h->stream));
+  long long total = 0;
+  HIPCHK(hipMemcpyAsync(&total, (const char *)h->d_select + DEV_SEL_OFFSETS_AT + (size_t)DEV_SEL_GRID * 8, sizeof(long long),
+                        hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const long long nout = total < max_out ? total : max_out;
+  if (nout > 0)
+    HIPCHK(hipMemcpy(cols_out, (const char *)h->d_select + DEV_SEL_LIST_AT, sizeof(int64_t) * (size_t)nout, hipMemcpyDeviceToHost));
+  *n_match = total;
+  return SAMSIM_OK;
+}
+
+int samsim_get_columns(samsim_handle *h, int64_t ncols, const int64_t *cols, samsim_state_soa *s, int32_t *status, int64_t *step,
+                       int32_t *layer) {
+  // every check first: a call that is refused writes nothing to the caller's buffers
+  if (!h || !cols || !s) return SAMSIM_ERR_ARG;
+  // the shape checks of check_soa, without its window: a list may be longer than the handle (duplicates)
+  if (!s->lay || !s->scal || !s->n_active || s->nlayer != h->cfg.nlayer) return SAMSIM_ERR_ARG;
+  if (s->narr != SAMSIM_NPROG && s->narr != SAMSIM_NARR) return SAMSIM_ERR_ARG;
+  if (ncols < 1 || ncols > SAMSIM_SELECT_MAX_OUT || s->ncol != ncols) return SAMSIM_ERR_ARG;
+  int rc;
+  for (int64_t j = 0; j < ncols; ++j)
+    if (cols[j] < 0 || cols[j] >= h->ncol) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
+  long long *d_cols = (long long *)((char *)h->d_select + DEV_SEL_LIST_AT);
+  const size_t N = (size_t)s->nlayer, w = (size_t)ncols;
+  // the list's positions in pieces as samsim_get_state cuts a window; the staging buffer also takes the per-column rows, one piece
+  const size_t pc = stage_cols(s->narr, N), rows = (size_t)s->narr * N;
+  const size_t lay_n = rows * (w < pc ? w : pc), col_n = (w * DEV_SEL_COLUMN_BYTES + 7) / 8;
+  HIPCHK(stage_for(h, lay_n > col_n ? lay_n : col_n));
+  HIPCHK(hipMemcpyAsync(d_cols, cols, sizeof(int64_t) * w, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(samsim_launch_gather_columns(h->scal, h->n_active, h->status, h->err_step, h->err_layer, d_cols, h->stage, h->ncol, (long long)w,
+                                      h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  {
+    const double *g_scal = h->stage;
+    const long long *g_step = (const long long *)(g_scal + (size_t)SAMSIM_NSCAL * w);
+    const int32_t *g_na = (const int32_t *)(g_step + w);
+    HIPCHK(hipMemcpy(s->scal, g_scal, sizeof(double) * SAMSIM_NSCAL * w, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s->n_active, g_na, sizeof(int32_t) * w, hipMemcpyDeviceToHost));
+    if (step) HIPCHK(hipMemcpy(step, g_step, sizeof(int64_t) * w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, g_na + w, sizeof(int32_t) * w, hipMemcpyDeviceToHost));
+    if (layer) HIPCHK(hipMemcpy(layer, g_na + 2 * w, sizeof(int32_t) * w, hipMemcpyDeviceToHost));
+  }
+  for (size_t p0 = 0; p0 < w; p0 += pc) {
+    const size_t pw = w - p0 < pc ? w - p0 : pc;
+    HIPCHK(samsim_launch_gather_layers(h->lay, d_cols + p0, h->n_active, h->status, h->flags, h->stage, (int)s->narr, (int)N, h->ncol,
+                                       (long long)pw, h->stepped ? 1 : 0, h->stream));
+    HIPCHK(copy_rows(s->lay + p0, w, h->stage, pw, pw, rows, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
   return SAMSIM_OK;
 }
 
