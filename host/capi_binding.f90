@@ -105,6 +105,16 @@ MODULE mo_samsim_capi
      TYPE(samsim_select_term) :: terms(SAMSIM_SELECT_MAX_TERMS)
   END TYPE samsim_selection
 
+  ! samsim_set_functionals: enum samsim_functional_kind and the description of one functional of a column's layer profile
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_FN_INTEGRAL = 0, SAMSIM_FN_MEAN = 1, SAMSIM_FN_MIN = 2, SAMSIM_FN_MAX = 3, &
+                                   SAMSIM_FN_DEPTH_OF_MIN = 4, SAMSIM_FN_DEPTH_OF_MAX = 5, SAMSIM_FN_CROSSING_DEPTH = 6, &
+                                   SAMSIM_FN_THICKNESS_WHERE = 7
+  INTEGER, PARAMETER :: SAMSIM_MAX_FUNCTIONALS = 8
+  TYPE, BIND(C) :: samsim_functional_spec
+     INTEGER(c_int32_t) :: struct_size, kind, array, origin, sense, reserved   ! array: enum samsim_layer_array (0-based)
+     REAL(c_double)     :: z_lo, z_hi, threshold, missing
+  END TYPE samsim_functional_spec
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -345,6 +355,22 @@ MODULE mo_samsim_capi
        TYPE(samsim_state_soa), INTENT(inout) :: s
        TYPE(c_ptr), VALUE :: status, step, layer
      END FUNCTION
+     !> evaluate n functionals of every column's layer profile on the device: samsim_func_slot(i) is then a slot of the ensemble
+     !! reductions, always current; n = 0 with c_null_ptr removes them
+     INTEGER(c_int) FUNCTION samsim_set_functionals(h, n, specs) BIND(C, name='samsim_set_functionals')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: n
+       TYPE(c_ptr), VALUE :: specs                       ! samsim_functional_spec [n] (c_loc of a TARGET array), or c_null_ptr
+     END FUNCTION
+     !> the value of functional index (0-based) in the columns [col0, col0+ncols)
+     INTEGER(c_int) FUNCTION samsim_get_functionals(h, index, col0, ncols, out) BIND(C, name='samsim_get_functionals')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: index
+       INTEGER(c_int64_t), VALUE :: col0, ncols
+       REAL(c_double), INTENT(out) :: out(*)
+     END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')
        IMPORT
@@ -411,5 +437,12 @@ CONTAINS
     INTEGER(c_int32_t) :: slot
     slot = 65536_c_int32_t + track*32_c_int32_t + field
   END FUNCTION samsim_track_slot
+
+  !> SAMSIM_FUNC_SLOT(i): the row of functional i (0-based) as a slot of the ensemble reductions
+  PURE FUNCTION samsim_func_slot(i) RESULT(slot)
+    INTEGER(c_int32_t), INTENT(in) :: i
+    INTEGER(c_int32_t) :: slot
+    slot = 131072_c_int32_t + i
+  END FUNCTION samsim_func_slot
 
 END MODULE mo_samsim_capi

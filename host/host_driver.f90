@@ -6,7 +6,7 @@
 !! New surface the reference does not have (SURVEY.md, introduction): a namelist file `samsim.nml`
 !!   &samsim_run   testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, restart_out, sites,
 !!                 profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every, members_thinner,
-!!                 members_max /
+!!                 members_max, permeable_psi_l /
 !! (col0 / ncol_total: this process owns the global columns col0 .. col0+ncol-1 of an ensemble of ncol_total -- one host
 !! process per GPU, contiguous column ranges, no exchange between them, SURVEY.md section 8e)
 !!   &samsim_flags <any flag of mo_data.f90:136-155 or scalar set by mo_init> /       (overrides init(testcase))
@@ -43,6 +43,7 @@ MODULE mo_data
   INTEGER(c_int64_t)  :: track_every = 0     !< > 0: time-domain diagnostics, sampled on the device after every track_every-th step: the ice thickness, and the surface temperature with the condition T_top >= 0 (dat_ens_track.dat at the end of the run)
   REAL(wp)            :: members_thinner = 0._wp   !< > 0 [m]: at the end of the run the members whose ice (the thickness slot) is thinner than this, selected on the device: their indices and scalars (dat_ens_members.dat) and their profiles (dat_ens_members_{T,S_bu,thick}.dat)
   INTEGER             :: members_max = 64    !< at most this many members are written, the first in column order
+  REAL(wp)            :: permeable_psi_l = 0._wp   !< > 0: at every output point the ensemble statistics of the thickness of the permeable ice (psi_l >= permeable_psi_l, the rule of fives: 0.05) and of the depth at which it begins, two column functionals evaluated on the device (dat_ens_permeable.dat)
   LOGICAL             :: by_site = .FALSE.   !< stats_by_site asked for and the run has more than one site: the handle carries the sites as group labels
   INTEGER             :: i_time, i_time_out
   REAL(wp)            :: fl_q_bottom = 0._wp, T_top = 0._wp, fl_sw = 0._wp, fl_rest = 0._wp, T2m = 0._wp, tank_depth = 0._wp
@@ -710,6 +711,38 @@ CONTAINS
     DEALLOCATE(cols)
   END SUBROUTINE output_members
 
+  !> The two functionals of permeable_psi_l > 0 (samsim_set_functionals), both of psi_l over the whole column: functional 0 the
+  !! thickness of the layers with psi_l >= permeable_psi_l -- the permeable part of the ice --, functional 1 the depth below the ice
+  !! surface of the first such layer, -1 in a column that has none.  The library keeps their rows current.
+  SUBROUTINE functionals_begin(h)
+    USE, INTRINSIC :: ieee_arithmetic, ONLY: ieee_value, ieee_positive_inf
+    TYPE(c_ptr), INTENT(in) :: h
+    TYPE(samsim_functional_spec), TARGET :: specs(2)
+    IF (.NOT. permeable_psi_l > 0._wp) RETURN
+    specs%struct_size = INT(c_sizeof(specs(1)), c_int32_t)
+    specs%array = INT(A_PSI_L - 1, c_int32_t); specs%origin = SAMSIM_PROFILE_FROM_TOP; specs%sense = 1; specs%reserved = 0
+    specs%z_lo = 0._wp; specs%z_hi = ieee_value(1._wp, ieee_positive_inf); specs%threshold = permeable_psi_l
+    specs(1)%kind = SAMSIM_FN_THICKNESS_WHERE; specs(1)%missing = 0._wp
+    specs(2)%kind = SAMSIM_FN_CROSSING_DEPTH;  specs(2)%missing = -1._wp
+    CALL samsim_check(samsim_set_functionals(h, 2_c_int32_t, c_loc(specs)), 'samsim_set_functionals')
+    OPEN(67, file='./output/dat_ens_permeable.dat', STATUS='replace', Recl=256)
+  END SUBROUTINE functionals_begin
+
+  !> One row per output point in dat_ens_permeable.dat: the time, then count, mean, min, max and standard deviation over the ensemble
+  !! of the permeable thickness and of the depth at which the permeable ice begins (samsim_get_ensemble_stats on the two functional
+  !! slots of functionals_begin).
+  SUBROUTINE output_permeable(h, time)
+    TYPE(c_ptr), INTENT(in) :: h
+    REAL(wp),    INTENT(in) :: time
+    INTEGER(c_int32_t) :: slots(2)
+    TYPE(samsim_stat)  :: q(2)
+    INTEGER :: j
+    IF (.NOT. permeable_psi_l > 0._wp) RETURN
+    slots = (/ samsim_func_slot(0_c_int32_t), samsim_func_slot(1_c_int32_t) /)
+    CALL samsim_check(samsim_get_ensemble_stats(h, 2_c_int32_t, slots, q), 'samsim_get_ensemble_stats')
+    WRITE(67, '(F14.1,2(I10,4ES24.16))') time, (q(j)%count, q(j)%mean, q(j)%min, q(j)%max, q(j)%std, j = 1, 2)
+  END SUBROUTINE output_permeable
+
   !> the units of dat_ens_profile_{T,S_bu,psi_l}_site<kk>.dat: array a = 1..3 of site s = 1..nsites.  nsites is at most
   !! SIZE(sites) = 16 (the namelist holds no more directories), so the units stay within 601..648 and <kk> within two digits.
   INTEGER FUNCTION site_unit(a, s)
@@ -779,6 +812,7 @@ CONTAINS
           CLOSE(59); CLOSE(60); CLOSE(61)
        END IF
     END IF
+    IF (permeable_psi_l > 0._wp) CLOSE(67)
     IF (hist_bins > 0) THEN
        CLOSE(56)
        IF (by_site) CLOSE(57)
@@ -992,6 +1026,7 @@ CONTAINS
     CALL samsim_check(samsim_set_state(h, st, 0_c_int64_t), 'samsim_set_state')
     IF (LEN_TRIM(restart_in) > 0) CALL read_restart(h, restart_in)
     CALL tracks_begin(h)
+    CALL functionals_begin(h)
     CALL samsim_check(samsim_set_output_window(h, INT(out_col - 1, c_int64_t), 1_c_int64_t), 'samsim_set_output_window')
     ALLOCATE(olay(1, cfg%nlayer, SAMSIM_NARR), oscal(1, SAMSIM_NSCAL), ona(1))
     o%ncols = 1; o%nlayer = cfg%nlayer; o%reserved = 0
@@ -1018,6 +1053,7 @@ CONTAINS
           CALL output_site(h, o%time)
           CALL output_hist(h, o%time)
           CALL output_sens(h, o%time)
+          CALL output_permeable(h, o%time)
           time = o%time
           thick1 = olay(1, 1, A_THICK)
           ! console progress line, mo_grotz.f90:371-381
@@ -1067,7 +1103,7 @@ PROGRAM SAMSIM
   LOGICAL         :: have_nml
   NAMELIST /samsim_run/ testcase, ncol, col0, ncol_total, device, out_col, perturb, description, max_steps, restart_in, &
        restart_out, sites, profile_bins, profile_dz, profile_origin, stats_by_site, hist_bins, hist_max, sens, track_every, &
-       members_thinner, members_max
+       members_thinner, members_max, permeable_psi_l
 
   testcase    = 1
   description = 'MI355X-native batched column solver'
@@ -1087,6 +1123,10 @@ PROGRAM SAMSIM
      END IF
      IF (.NOT. members_thinner >= 0._wp .OR. members_max < 1 .OR. members_max > SAMSIM_SELECT_MAX_OUT) THEN
         PRINT *, 'samsim_run: members_thinner must be >= 0 and members_max must lie in 1 ..', SAMSIM_SELECT_MAX_OUT
+        STOP 4
+     END IF
+     IF (.NOT. permeable_psi_l >= 0._wp .OR. permeable_psi_l > HUGE(1._wp)) THEN
+        PRINT *, 'samsim_run: permeable_psi_l must be finite and >= 0'
         STOP 4
      END IF
   END IF

@@ -579,6 +579,78 @@ int samsim_select_columns(samsim_handle *h, const samsim_selection *sel, int64_t
 int samsim_get_columns(samsim_handle *h, int64_t ncols, const int64_t *cols, samsim_state_soa *s,
                        int32_t *status, int64_t *step, int32_t *layer);
 
+/* Column functionals: vertical integrals, extrema and crossing depths as slots.  Every reduction above consumes a slot, one
+ * double[ncol] row; what a sea-ice user asks of a column is mostly a functional of its layer profile -- how thick the permeable part
+ * of the ice is (psi_l >= 0.05), how deep the -5 degC isotherm lies, the mean salinity of the upper 0.5 m, the depth-integrated brine
+ * volume, the largest Rayleigh number and where it sits.  samsim_set_functionals names up to SAMSIM_MAX_FUNCTIONALS of them; the
+ * device evaluates each into a row of its own, and SAMSIM_FUNC_SLOT(i) is that row wherever a slot is accepted.  The entry points
+ * below were added without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only, found by symbol as the group, histogram,
+ * sensitivity, track and select functions are.  They read the state and write only their own rows.
+ *
+ *   Columns.  Every column c < ncol is evaluated, whatever its status, from the bytes samsim_get_state would return for it now:
+ *     S_abs with the health check's clamp S_abs >= 0, and S_bu = S_abs/m where m != 0, under exactly that function's conditions (after a
+ *     step; status 0; the clamp not in a column uploaded since the last step; the stored values elsewhere).  Clamp and quotient are
+ *     formed in registers, as the track sampler forms them: nothing is written to the ensemble.  Na = n_active[c] clamped to
+ *     [0, nlayer].  The consumers decide by status which columns count, as they do for every slot; a stopped column carries the value
+ *     of the state it froze with (SAMSIM_SELECT_STOPPED / ANY read it).
+ *   Depth.  Z_0 = 0, Z_k = Z_{k-1} + thick(k) by sequential double additions, k ascending; H = Z_Na.  origin is an enum
+ *     samsim_profile_origin.  Layer k, 1 <= k <= Na, covers [lo_k, hi_k): FROM_TOP [Z_{k-1}, Z_k), FROM_BOTTOM [H - Z_k, H - Z_{k-1}).
+ *     Window [z_lo, z_hi): z_lo >= 0 finite, z_hi > z_lo, z_hi = +inf allowed (the whole column).  With mn(x, y) = x < y ? x : y and
+ *     mx(x, y) = x > y ? x : y:  e0_k = mx(lo_k, z_lo), e1_k = mn(hi_k, z_hi), o_k = e1_k - e0_k.  Layer k is IN THE WINDOW if and only
+ *     if o_k > 0 (a layer of zero thickness never is, nor one whose edge only touches the window).  Snow is not part of the coordinate.
+ *   Layer value.  a_k is the value of `array` (enum samsim_layer_array) in layer k as above.
+ *   Condition (CROSSING_DEPTH and THICKNESS_WHERE only).  sense +1: a_k >= threshold.  sense -1: a_k < threshold.  A NaN satisfies
+ *     neither.
+ *   Kinds.  All sums run over the in-window layers in ascending k, from 0.0; products are rounded, then added; no fused multiply-add.
+ *     SAMSIM_FN_INTEGRAL: W = sum o_k*a_k; 0.0 with no layer in the window.
+ *     SAMSIM_FN_MEAN: W / L with L = sum o_k, one IEEE division.
+ *     SAMSIM_FN_MIN / SAMSIM_FN_MAX: the extreme of a_k.  The first in-window a_k that is not a NaN begins it; a later a_k replaces it when
+ *       a_k < min (a_k > max).  So the first attainment in ascending k is kept and a NaN never becomes an extreme.
+ *     SAMSIM_FN_DEPTH_OF_MIN / SAMSIM_FN_DEPTH_OF_MAX: 0.5 * (lo_k + hi_k) of that layer: the sum is rounded, then halved; the layer's
+ *       bounds are unclipped.
+ *     SAMSIM_FN_CROSSING_DEPTH: e0_k = mx(lo_k, z_lo) of the first in-window layer, counted from the origin, in which the condition
+ *       holds: the smallest such k FROM_TOP, the largest FROM_BOTTOM.
+ *     SAMSIM_FN_THICKNESS_WHERE: sum o_k over the in-window layers in which the condition holds; 0.0 if there are none.
+ *     missing: any double, NaN included: the value where MEAN, MIN, MAX, DEPTH_OF_* or CROSSING_DEPTH have no layer to speak of -- an
+ *       empty window, Na == 0, only NaNs for the extremes, the condition never met.  With missing = -1 and v0 = 0, entry 0 of a
+ *       histogram holds the columns in which it never happened, as with STEP_FIRST of the tracks.
+ *     Every value is a fixed sequence of IEEE operations on the column's own data: a host reproduces it to the bit from samsim_get_state.
+ *   When.  The rows are always current: they describe the state samsim_get_state would return now.  The library keeps a dirty flag,
+ *     set by stepping, samsim_set_state, samsim_set_status and samsim_set_functionals; every entry point that resolves a
+ *     SAMSIM_FUNC_SLOT, and samsim_get_functionals, evaluates first when the flag is set: one kernel on the handle's first stream,
+ *     after the wait every getter makes.  Calls that use no functional slot launch nothing new.
+ *   samsim_set_functionals.  n in 1..SAMSIM_MAX_FUNCTIONALS allocates [n][ncol] doubles on the device (64-bit offsets).  n == 0 with
+ *     NULL removes them and frees the rows (also when none was set).  A call that is refused leaves the previous ones in force.  The
+ *     specs belong to the caller, as the labels do: they are not part of a checkpoint; samsim_destroy frees the rows.
+ *   samsim_get_functionals.  out[ncols] = the window [col0, col0 + ncols) of the row of functional `index`.
+ *   Slots.  SAMSIM_FUNC_SLOT(i) with i < n of the functionals in force is accepted wherever a slot is -- samsim_get_ensemble_stats,
+ *     samsim_get_group_stats, samsim_get_histogram, the slots of samsim_get_covariance, predictor_slot of
+ *     samsim_get_profile_regression, the terms of samsim_select_columns -- and resolves to that row; without functionals, or out of
+ *     range, it is the SAMSIM_ERR_ARG of any bad slot.  So the histogram of the permeable thickness per site is a
+ *     samsim_get_histogram by group, the covariance of the isotherm depth with dT2m a samsim_get_covariance, and the members with no
+ *     permeable layer at all a samsim_select_columns.
+ *   Not in scope.  The tracks do not take a functional as an observable (enum samsim_observable_kind is closed), and the tracer state
+ *     is not an array of this call.
+ *   Errors, all found before any device work, in this order.  samsim_set_functionals: SAMSIM_ERR_ARG for h NULL; n outside
+ *     0..SAMSIM_MAX_FUNCTIONALS; specs NULL with n > 0 (or not NULL with n == 0); then per spec in order: SAMSIM_ERR_ABI for a wrong
+ *     struct_size; SAMSIM_ERR_ARG for a bad kind, array or origin; sense not +1 or -1 for the two kinds with a condition, or not 0 for
+ *     the other kinds; a non-finite threshold with sense != 0; a non-finite or negative z_lo; a NaN z_hi or z_hi <= z_lo;
+ *     reserved != 0.  SAMSIM_ERR_NOMEM if the rows cannot be allocated (the previous functionals stay).  samsim_get_functionals:
+ *     SAMSIM_ERR_ARG for NULL pointers, no functionals set, index outside [0, n), a window outside [0, ncol); nothing is written to out
+ *     when a call is refused. */
+#define SAMSIM_MAX_FUNCTIONALS 8
+#define SAMSIM_FUNC_SLOT(i) (0x20000 + (i))
+enum samsim_functional_kind {
+  SAMSIM_FN_INTEGRAL = 0, SAMSIM_FN_MEAN, SAMSIM_FN_MIN, SAMSIM_FN_MAX,
+  SAMSIM_FN_DEPTH_OF_MIN, SAMSIM_FN_DEPTH_OF_MAX,
+  SAMSIM_FN_CROSSING_DEPTH, SAMSIM_FN_THICKNESS_WHERE, SAMSIM_NFN };
+typedef struct samsim_functional_spec {   /* 56 bytes */
+  int32_t struct_size, kind, array, origin, sense, reserved;
+  double  z_lo, z_hi, threshold, missing;
+} samsim_functional_spec;
+int samsim_set_functionals(samsim_handle *h, int32_t n, const samsim_functional_spec *specs);
+int samsim_get_functionals(samsim_handle *h, int32_t index, int64_t col0, int64_t ncols, double *out /*[ncols]*/);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

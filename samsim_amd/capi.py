@@ -170,8 +170,35 @@ def track_slot(track, field) -> int:
     return 0x10000 + int(track) * 32 + (TF[field] if isinstance(field, str) else int(field))
 
 
+MAX_FUNCTIONALS = 8         # SAMSIM_MAX_FUNCTIONALS
+# enum samsim_functional_kind
+FUNCTIONAL_KINDS = ["integral", "mean", "min", "max", "depth_of_min", "depth_of_max", "crossing_depth", "thickness_where"]
+FN = {n: i for i, n in enumerate(FUNCTIONAL_KINDS)}
+
+
+class FunctionalSpec(C.Structure):
+    """samsim_functional_spec: one functional of a column's layer profile over the depth window [z_lo, z_hi), with the condition
+    a_k >= threshold (sense +1) or a_k < threshold (sense -1) for "crossing_depth" and "thickness_where" """
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("array", C.c_int32), ("origin", C.c_int32), ("sense", C.c_int32),
+                ("reserved", C.c_int32), ("z_lo", C.c_double), ("z_hi", C.c_double), ("threshold", C.c_double), ("missing", C.c_double)]
+
+    @staticmethod
+    def make(kind, array, origin="top", z_lo=0.0, z_hi=np.inf, sense=0, threshold=0.0, missing=np.nan) -> "FunctionalSpec":
+        """kind from FUNCTIONAL_KINDS, array from ARRAYS, origin from PROFILE_ORIGINS (names or their numbers)"""
+        k = FN[kind] if isinstance(kind, str) else int(kind)
+        a = A[array] if isinstance(array, str) else int(array)
+        o = PROFILE_ORIGINS[origin] if isinstance(origin, str) else int(origin)
+        return FunctionalSpec(C.sizeof(FunctionalSpec), k, a, o, int(sense), 0, float(z_lo), float(z_hi), float(threshold), float(missing))
+
+
+def func_slot(i) -> int:
+    """SAMSIM_FUNC_SLOT(i): the row of functional i as a slot of ensemble_stats, group_stats, histogram, covariance,
+    profile_regression and select"""
+    return 0x20000 + int(i)
+
+
 def _slot(name) -> int:
-    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot gives it"""
+    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot or func_slot gives it"""
     if isinstance(name, (int, np.integer)):
         return int(name)
     return -1 if name == "N_active" else S[name]
@@ -417,6 +444,12 @@ class Solver:
         select_sig = {"select_columns": [vp, C.POINTER(Selection), i64, C.c_void_p, C.POINTER(C.c_int64)],
                       "get_columns": [vp, i64, C.c_void_p, C.POINTER(StateSoA), C.c_void_p, C.c_void_p, C.c_void_p]}
         for n, a in select_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the column functionals
+        func_sig = {"set_functionals": [vp, C.c_int32, C.POINTER(FunctionalSpec)], "get_functionals": [vp, C.c_int32, i64, i64, C.c_void_p]}
+        for n, a in func_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -783,6 +816,29 @@ class Solver:
         self._chk(self._f("get_columns")(self._h, n, cols.ctypes.data, C.byref(s), status.ctypes.data, step.ctypes.data, layer.ctypes.data),
                   "get_columns")
         return st, (status, step, layer)
+
+    # -- column functionals
+    def set_functionals_raw(self, n, specs):
+        """samsim_set_functionals with the arguments as given (no checks on this side): specs a ctypes array of FunctionalSpec or None"""
+        self._chk(self._f("set_functionals")(self._h, int(n), specs), "set_functionals")
+        self.nfunctionals = int(n) if specs is not None else 0
+
+    def set_functionals(self, specs):
+        """evaluate the functionals `specs` (FunctionalSpec, at most MAX_FUNCTIONALS) of every column's layer profile on the device
+        (samsim_set_functionals): func_slot(i) is then the row of specs[i] wherever a slot is accepted, always current.
+        set_functionals(None) removes them"""
+        if specs is None:
+            return self.set_functionals_raw(0, None)
+        specs = list(specs)
+        self.set_functionals_raw(len(specs), (FunctionalSpec * max(1, len(specs)))(*specs))
+
+    def functionals(self, index, col0: int = 0, ncols: int | None = None) -> np.ndarray:
+        """float64 [ncols]: the value of functional `index` in the columns [col0, col0 + ncols), stopped ones included
+        (samsim_get_functionals)"""
+        n = self.ncol - col0 if ncols is None else ncols
+        buf = np.zeros(max(0, n))
+        self._chk(self._f("get_functionals")(self._h, int(index), col0, n, buf.ctypes.data), "get_functionals")
+        return buf
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "samsim_device.h"
+#include "samsim_functionals.h"
 #include "samsim_groups.h"
 #include "samsim_hist.h"
 #include "samsim_select.h"
@@ -80,6 +81,10 @@ struct samsim_handle {
   int32_t ntracks = 0;         // 0: no tracking
   long long track_every = 0;   // a sample follows the step that brings clk.step to a multiple of it
   TrackDev track[SAMSIM_MAX_TRACKS]{};
+  double *func_rows = nullptr; // [nfunc][ncol] rows of the column functionals (samsim_set_functionals), evaluated by func_refresh()
+  int32_t nfunc = 0;           // 0: no functionals
+  bool func_dirty = true;      // the state changed since the rows were evaluated (stepping, set_state, set_status, set_functionals)
+  samsim_functional_spec func[SAMSIM_MAX_FUNCTIONALS]{};
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -395,6 +400,7 @@ int launch_cut(samsim_handle *h, long long nsteps, bool sample) {
     }
   }
   h->stepped = true;
+  h->func_dirty = true;
   advance_clock(h, nsteps);
   return SAMSIM_OK;
 }
@@ -415,9 +421,12 @@ int launch(samsim_handle *h, long long nsteps) {
   return SAMSIM_OK;
 }
 
-// a slot of the statistics: an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE, or SAMSIM_TRACK_SLOT(track, field) of the tracks in force
+// a slot of the statistics: an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE, SAMSIM_TRACK_SLOT(track, field) of the tracks in force, or
+// SAMSIM_FUNC_SLOT(i) of the functionals in force
+bool func_slot(int32_t slot) { return slot >= SAMSIM_FUNC_SLOT(0); }
 bool good_slot(const samsim_handle *h, int32_t slot) {
   if (slot == SAMSIM_STAT_N_ACTIVE || (slot >= 0 && slot < SAMSIM_NSCAL)) return true;
+  if (func_slot(slot)) return h->func_rows && slot - SAMSIM_FUNC_SLOT(0) < h->nfunc;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks && o >= 0 && o / 32 < h->ntracks && o % 32 < SAMSIM_NTF;
 }
@@ -425,6 +434,7 @@ bool good_slot(const samsim_handle *h, int32_t slot) {
 const double *slot_row(const samsim_handle *h, int32_t slot) {
   if (slot == SAMSIM_STAT_N_ACTIVE) return nullptr;
   if (slot < SAMSIM_NSCAL) return h->scal + (size_t)slot * (size_t)h->ncol;
+  if (func_slot(slot)) return h->func_rows + (size_t)(slot - SAMSIM_FUNC_SLOT(0)) * (size_t)h->ncol;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks + ((size_t)(o / 32) * SAMSIM_NTF + (size_t)(o % 32)) * (size_t)h->ncol;
 }
@@ -438,6 +448,54 @@ int use(samsim_handle *h, bool stepping = false) {
     if (h->stream2) HIPCHK(hipStreamSynchronize(h->stream2));
     h->other_work = true;
   }
+  return SAMSIM_OK;
+}
+
+// The walks of one evaluation: the distinct rows each functional needs -- its array; S_abs and m for S_bu once the kernel has run, as
+// samsim_get_state then forms the quotient -- are deduplicated and the functionals put into groups of at most DEV_FUNC_GROUP_ROWS rows,
+// in their order: a functional joins the current group if the union of the rows still fits, else it begins the next.
+void func_plan(const samsim_handle *h, FuncParams *p) {
+  int g = 0;
+  p->gn[0] = 0;
+  for (int i = 0; i < h->nfunc; ++i) {
+    const samsim_functional_spec &s = h->func[i];
+    FuncDev &d = p->f[i];
+    d = FuncDev{s.kind, s.origin, s.sense, DEV_FUNC_PLAIN, 0, 0, 0, 0, s.z_lo, s.z_hi, s.threshold, s.missing};
+    int need[2] = {s.array, -1};
+    if (s.array == SAMSIM_A_S_ABS) d.mode = DEV_FUNC_S_ABS;
+    if (s.array == SAMSIM_A_S_BU && h->stepped) { d.mode = DEV_FUNC_S_BU; need[0] = SAMSIM_A_S_ABS; need[1] = SAMSIM_A_M; }
+    auto find = [&](int a) { for (int j = 0; j < p->gn[g]; ++j) if (p->grow[g][j] == a) return j; return -1; };
+    int missing = 0;
+    for (int a : need) if (a >= 0 && find(a) < 0) ++missing;
+    if (p->gn[g] + missing > DEV_FUNC_GROUP_ROWS) p->gn[++g] = 0;
+    int at[2] = {0, 0};
+    for (int j = 0; j < 2; ++j) {
+      if (need[j] < 0) continue;
+      at[j] = find(need[j]);
+      if (at[j] < 0) { at[j] = p->gn[g]; p->grow[g][p->gn[g]++] = need[j]; }
+    }
+    d.group = g; d.ia = at[0]; d.ib = at[1];
+    if (s.origin == SAMSIM_PROFILE_FROM_BOTTOM) p->need_H = 1;
+  }
+  p->ngroups = g + 1;
+}
+
+// the rows of the functionals brought up to date, on the handle's first stream: one kernel, and only when the state changed since the
+// last evaluation.  Called behind use() by samsim_get_functionals and by every consumer that was handed a SAMSIM_FUNC_SLOT.
+int func_refresh(samsim_handle *h) {
+  if (!h->func_rows || !h->func_dirty) return SAMSIM_OK;
+  FuncParams p{};
+  p.lay = h->lay; p.n_active = h->n_active; p.status = h->status; p.flags = h->flags;
+  p.rows = h->func_rows;
+  p.ncol = h->ncol; p.N = h->cfg.nlayer; p.nf = h->nfunc; p.stepped = h->stepped ? 1 : 0;
+  func_plan(h, &p);
+  HIPCHK(samsim_launch_functionals(&p, h->stream));
+  h->func_dirty = false;
+  return SAMSIM_OK;
+}
+int func_refresh_for(samsim_handle *h, int32_t nslots, const int32_t *slots) {
+  for (int i = 0; i < nslots; ++i)
+    if (func_slot(slots[i])) return func_refresh(h);
   return SAMSIM_OK;
 }
 
@@ -546,6 +604,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->err_layer); (void)hipFree(h->err_step); (void)hipFree(h->work);
   (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
   (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens); (void)hipFree(h->tracks);
+  (void)hipFree(h->func_rows);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -643,6 +702,7 @@ int samsim_set_state(samsim_handle *h, const samsim_state_soa *s, int64_t col0) 
   if (rc) return rc;
   const size_t N = (size_t)s->nlayer, nc = (size_t)h->ncol, w = (size_t)s->ncol;
   for (size_t i = 0; i < w; ++i) if (s->n_active[i] < 1 || s->n_active[i] > (int)N) return SAMSIM_ERR_ARG;
+  h->func_dirty = true;
   HIPCHK(hipStreamSynchronize(h->stream));
   // the window in pieces of at most stage_cols columns: rows [narr][N] of the piece's columns are gathered from the caller's
   // [narr][N][w] into the staging buffer by one 2D copy, then scattered into the device layout
@@ -833,6 +893,7 @@ int samsim_set_status(samsim_handle *h, const int32_t *status, const int64_t *st
   int rc = use(h);
   if (rc) return rc;
   if (!status || col0 < 0 || ncols < 0 || col0 + ncols > h->ncol) return SAMSIM_ERR_ARG;
+  h->func_dirty = true;
   HIPCHK(hipStreamSynchronize(h->stream));
   const size_t w = (size_t)ncols;
   HIPCHK(hipMemcpy(h->status + col0, status, sizeof(int32_t) * w, hipMemcpyHostToDevice));
@@ -938,6 +999,8 @@ int samsim_get_ensemble_stats(samsim_handle *h, int32_t nslots, const int32_t *s
   if (nslots < 0 || (nslots > 0 && (!slots || !out))) return SAMSIM_ERR_ARG;
   for (int i = 0; i < nslots; ++i)
     if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
+  rc = func_refresh_for(h, nslots, slots);
+  if (rc) return rc;
   if (!h->d_stat) HIPCHK(hipMalloc(&h->d_stat, sizeof(StatPartial) * kStatGrid));
   StatPartial *d_part = (StatPartial *)h->d_stat;
   std::vector<StatPartial> part(kStatGrid);
@@ -1054,6 +1117,8 @@ int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slot
     if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
   int rc = use(h);
   if (rc) return rc;
+  rc = func_refresh_for(h, nslots, slots);
+  if (rc) return rc;
   if (!h->d_group) HIPCHK(hipMalloc(&h->d_group, kGroupScratch));
   GroupPartial *d_part = (GroupPartial *)h->d_group;
   samsim_stat *d_out = (samsim_stat *)((char *)h->d_group + kGroupPartBytes);
@@ -1095,6 +1160,8 @@ int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins 
   if (by_group != 0 && by_group != 1) return SAMSIM_ERR_ARG;
   if (by_group && !h->groups) return SAMSIM_ERR_ARG;
   rc = use(h);
+  if (rc) return rc;
+  rc = func_refresh_for(h, 1, &slot);
   if (rc) return rc;
   if (!h->d_hist) HIPCHK(hipMalloc(&h->d_hist, kHistScratch));
   const int ng = by_group ? h->ngroups : 1;
@@ -1150,6 +1217,8 @@ int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots
   if (!good_group(h, group)) return SAMSIM_ERR_ARG;
   int rc = use(h);
   if (rc) return rc;
+  rc = func_refresh_for(h, nslots, slots);
+  if (rc) return rc;
   if (!h->d_sens) HIPCHK(hipMalloc(&h->d_sens, kSensScratch));
   double *d_part = (double *)h->d_sens;
   CovResult *d_out = (CovResult *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
@@ -1175,6 +1244,8 @@ int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request
   if (!good_slot(h, predictor_slot)) return SAMSIM_ERR_ARG;
   if (!good_group(h, group)) return SAMSIM_ERR_ARG;
   rc = use(h);
+  if (rc) return rc;
+  rc = func_refresh_for(h, 1, &predictor_slot);
   if (rc) return rc;
   if (!h->d_sens) HIPCHK(hipMalloc(&h->d_sens, kSensScratch));
   SensProfPartial *d_part = (SensProfPartial *)h->d_sens;
@@ -1322,6 +1393,8 @@ int samsim_select_columns(samsim_handle *h, const samsim_selection *sel, int64_t
   if (max_out < 0 || max_out > SAMSIM_SELECT_MAX_OUT || (max_out > 0 && !cols_out)) return SAMSIM_ERR_ARG;
   int rc = use(h);
   if (rc) return rc;
+  for (int i = 0; i < sel->nterms && !rc; ++i) rc = func_refresh_for(h, 1, &sel->terms[i].slot);
+  if (rc) return rc;
   if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
   SelParams p{};
   for (int i = 0; i < sel->nterms; ++i) p.t[i] = SelTerm{slot_row(h, sel->terms[i].slot), sel->terms[i].lo, sel->terms[i].hi};
@@ -1388,6 +1461,62 @@ int samsim_get_columns(samsim_handle *h, int64_t ncols, const int64_t *cols, sam
     HIPCHK(copy_rows(s->lay + p0, w, h->stage, pw, pw, rows, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
+  return SAMSIM_OK;
+}
+
+// the checks of one functional, in the order samsim.h gives
+static int check_functional_spec(const samsim_functional_spec &s) {
+  if (s.struct_size != (int32_t)sizeof(samsim_functional_spec)) return SAMSIM_ERR_ABI;
+  if (s.kind < 0 || s.kind >= SAMSIM_NFN) return SAMSIM_ERR_ARG;
+  if (s.array < 0 || s.array >= SAMSIM_NARR) return SAMSIM_ERR_ARG;
+  if (s.origin != SAMSIM_PROFILE_FROM_TOP && s.origin != SAMSIM_PROFILE_FROM_BOTTOM) return SAMSIM_ERR_ARG;
+  const bool cond = s.kind == SAMSIM_FN_CROSSING_DEPTH || s.kind == SAMSIM_FN_THICKNESS_WHERE;
+  if (cond ? (s.sense != 1 && s.sense != -1) : s.sense != 0) return SAMSIM_ERR_ARG;
+  if (s.sense != 0 && !std::isfinite(s.threshold)) return SAMSIM_ERR_ARG;
+  if (!std::isfinite(s.z_lo) || s.z_lo < 0.0) return SAMSIM_ERR_ARG;
+  if (std::isnan(s.z_hi) || !(s.z_hi > s.z_lo)) return SAMSIM_ERR_ARG;
+  if (s.reserved != 0) return SAMSIM_ERR_ARG;
+  return SAMSIM_OK;
+}
+
+int samsim_set_functionals(samsim_handle *h, int32_t n, const samsim_functional_spec *specs) {
+  // every check first: a call that is refused leaves the previous functionals in force
+  if (!h) return SAMSIM_ERR_ARG;
+  if (n < 0 || n > SAMSIM_MAX_FUNCTIONALS) return SAMSIM_ERR_ARG;
+  if ((n > 0 && !specs) || (n == 0 && specs)) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < n; ++i) {
+    const int rc = check_functional_spec(specs[i]);
+    if (rc) return rc;
+  }
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  double *rows = nullptr;
+  if (n > 0 && dalloc(&rows, (size_t)n * (size_t)h->ncol) != hipSuccess) {
+    (void)hipGetLastError();
+    return SAMSIM_ERR_NOMEM;
+  }
+  (void)hipFree(h->func_rows);
+  h->func_rows = rows;
+  h->nfunc = n;
+  h->func_dirty = true;
+  static_assert(sizeof(samsim_functional_spec) == 56, "samsim_functional_spec of samsim.h");
+  for (int i = 0; i < n; ++i) h->func[i] = specs[i];
+  return SAMSIM_OK;
+}
+
+int samsim_get_functionals(samsim_handle *h, int32_t index, int64_t col0, int64_t ncols, double *out) {
+  if (!h || !out) return SAMSIM_ERR_ARG;
+  if (!h->func_rows) return SAMSIM_ERR_ARG;
+  if (index < 0 || index >= h->nfunc) return SAMSIM_ERR_ARG;
+  if (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  rc = func_refresh(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  HIPCHK(hipMemcpy(out, h->func_rows + (size_t)index * (size_t)h->ncol + (size_t)col0, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost));
   return SAMSIM_OK;
 }
 
