@@ -115,6 +115,19 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: z_lo, z_hi, threshold, missing
   END TYPE samsim_functional_spec
 
+  ! samsim_set_sensors: enum samsim_sensor_kind, enum samsim_sensor_interp, the description of one sensor, and enum
+  ! samsim_score_field, the rows of the per-column misfit
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_SENSOR_PROFILE = 0, SAMSIM_SENSOR_SCALAR = 1, SAMSIM_SENSOR_ICE_THICKNESS = 2
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_SENSOR_STEP = 0, SAMSIM_SENSOR_LINEAR = 1
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_SF_N_LAST = 0, SAMSIM_SF_J_LAST = 1, SAMSIM_SF_B_LAST = 2, SAMSIM_SF_W_LAST = 3, &
+                                   SAMSIM_SF_N_SUM = 4, SAMSIM_SF_J_SUM = 5, SAMSIM_SF_B_SUM = 6, SAMSIM_SF_W_SUM = 7, &
+                                   SAMSIM_SF_CALLS = 8
+  INTEGER, PARAMETER :: SAMSIM_MAX_SENSORS = 32, SAMSIM_NSF = 9
+  TYPE, BIND(C) :: samsim_sensor_spec
+     INTEGER(c_int32_t) :: struct_size, kind, id, origin, interp, reserved   ! id: enum samsim_layer_array or samsim_scalar (0-based)
+     REAL(c_double)     :: z, missing
+  END TYPE samsim_sensor_spec
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -371,6 +384,50 @@ MODULE mo_samsim_capi
        INTEGER(c_int64_t), VALUE :: col0, ncols
        REAL(c_double), INTENT(out) :: out(*)
      END FUNCTION
+     !> name n sensors and allocate the score rows [SAMSIM_NSF][ncol], all zero: samsim_score_slot(field) is then a slot of the
+     !! ensemble reductions; n = 0 with c_null_ptr removes sensors and rows
+     INTEGER(c_int) FUNCTION samsim_set_sensors(h, n, specs) BIND(C, name='samsim_set_sensors')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: n
+       TYPE(c_ptr), VALUE :: specs                       ! samsim_sensor_spec [n] (c_loc of a TARGET array), or c_null_ptr
+     END FUNCTION
+     !> y [n][ncols] (C order): the value of every sensor for the columns cols (0-based, any order, duplicates allowed)
+     INTEGER(c_int) FUNCTION samsim_get_sensor_values(h, ncols, cols, y) BIND(C, name='samsim_get_sensor_values')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: ncols
+       INTEGER(c_int64_t), INTENT(in) :: cols(*)
+       REAL(c_double), INTENT(out) :: y(*)
+     END FUNCTION
+     !> add the weighted squared differences against obs [n] (NaN: no observation) to the score rows of the running columns --
+     !! group >= 0: of those with that label --; weight [n] (c_loc) or c_null_ptr for 1.0
+     INTEGER(c_int) FUNCTION samsim_score(h, obs, weight, group) BIND(C, name='samsim_score')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       REAL(c_double), INTENT(in) :: obs(*)
+       TYPE(c_ptr), VALUE :: weight
+       INTEGER(c_int32_t), VALUE :: group
+     END FUNCTION
+     !> the window [col0, col0 + ncols) of the score rows, out [SAMSIM_NSF][ncols] (C order)
+     INTEGER(c_int) FUNCTION samsim_get_scores(h, col0, ncols, out) BIND(C, name='samsim_get_scores')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: col0, ncols
+       REAL(c_double), INTENT(out) :: out(*)
+     END FUNCTION
+     !> restart: put back what samsim_get_scores returned for that window
+     INTEGER(c_int) FUNCTION samsim_set_score_state(h, col0, ncols, rows) BIND(C, name='samsim_set_score_state')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: col0, ncols
+       REAL(c_double), INTENT(in) :: rows(*)
+     END FUNCTION
+     !> every score row back to 0.0
+     INTEGER(c_int) FUNCTION samsim_reset_scores(h) BIND(C, name='samsim_reset_scores')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+     END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')
        IMPORT
@@ -444,5 +501,12 @@ CONTAINS
     INTEGER(c_int32_t) :: slot
     slot = 131072_c_int32_t + i
   END FUNCTION samsim_func_slot
+
+  !> SAMSIM_SCORE_SLOT(field): a row of the per-column misfit (SAMSIM_SF_*) as a slot of the ensemble reductions
+  PURE FUNCTION samsim_score_slot(field) RESULT(slot)
+    INTEGER(c_int32_t), INTENT(in) :: field
+    INTEGER(c_int32_t) :: slot
+    slot = 196608_c_int32_t + field
+  END FUNCTION samsim_score_slot
 
 END MODULE mo_samsim_capi

@@ -651,6 +651,94 @@ typedef struct samsim_functional_spec {   /* 56 bytes */
 int samsim_set_functionals(samsim_handle *h, int32_t n, const samsim_functional_spec *specs);
 int samsim_get_functionals(samsim_handle *h, int32_t index, int64_t col0, int64_t ncols, double *out /*[ncols]*/);
 
+/* Sensors and the per-column misfit: the ensemble scored against observations.  Everything above describes the ensemble; a perturbed
+ * ensemble is run to be held against data -- a thermistor string's temperatures, the bulk salinity of a core's sections, the ice
+ * thickness and snow depth of a mass-balance buoy.  samsim_set_sensors names up to SAMSIM_MAX_SENSORS sensors; the device forms the
+ * model's equivalent y_i of each per column (the observation operator), samsim_get_sensor_values returns it for a list of columns,
+ * and samsim_score adds one weighted sum of squared differences per column against an observation vector to nine rows kept on the
+ * device, over as many observation times as the run has.  SAMSIM_SCORE_SLOT(field) is such a row wherever a slot is accepted: the
+ * histogram of the misfit, its statistics per site, its covariance with dT2m (the gradient a calibration follows), and
+ * samsim_select_columns for the members under a misfit bound.  The entry points below were added without a change of
+ * SAMSIM_ABI_VERSION (it stays 6): new symbols only, found by symbol as the functional functions are.  They read the state and write
+ * only their own rows.
+ *
+ *   Columns.  Every column is evaluated, whatever its status, from the bytes samsim_get_state would return for it now: S_abs with
+ *     the health check's clamp S_abs >= 0, and S_bu = S_abs/m where m != 0, under exactly that function's conditions (after a step;
+ *     status 0; the clamp not in a column uploaded since the last step; the stored values elsewhere).  Clamp and quotient are formed in
+ *     registers, as the functionals form them: nothing is written to the ensemble.  Na = n_active[c] clamped to [0, nlayer].
+ *   Depth.  Z_0 = 0, Z_k = Z_{k-1} + thick(k) by sequential double additions, k ascending; H = Z_Na.  origin is an enum
+ *     samsim_profile_origin.  Layer k, 1 <= k <= Na, covers [lo_k, hi_k): FROM_TOP [Z_{k-1}, Z_k), FROM_BOTTOM [H - Z_k, H - Z_{k-1}).
+ *     Snow is not part of the coordinate.
+ *   Layer value.  a_k is the value of array `id` (enum samsim_layer_array) in layer k as above.
+ *   Kinds.
+ *     SAMSIM_SENSOR_SCALAR: the stored slot `id` (enum samsim_scalar), e.g. the snow depth.  origin, interp and z must be 0.
+ *     SAMSIM_SENSOR_ICE_THICKNESS: H (SAMSIM_S_THICKNESS holds the last output point's).  id, origin, interp and z must be 0.
+ *     SAMSIM_SENSOR_PROFILE: array `id` at depth z >= 0, finite, measured from `origin`.  The containing layer is the smallest k in
+ *       1..Na with lo_k <= z && z < hi_k (a layer of zero thickness never contains a sensor).  Without one -- the sensor lies below the
+ *       ice, or Na == 0 -- y = missing and the sensor is NOT IN THE ICE for this column; SCALAR and ICE_THICKNESS sensors always are.
+ *       SAMSIM_SENSOR_STEP: y = a_k.
+ *       SAMSIM_SENSOR_LINEAR: between the midpoints c_k = 0.5 * (lo_k + hi_k) (the sum is rounded, then halved) of layer k and of its
+ *         neighbour j on the side of z: where z >= c_k the adjacent layer with the next larger coordinate (k + 1 FROM_TOP, k - 1
+ *         FROM_BOTTOM), else the one on the other side.  j outside 1..Na: y = a_k (constant in the outer half-layers).  Otherwise
+ *         (c_a, a_a) is that of the two layers with the smaller coordinate -- FROM_TOP the one with the smaller index, FROM_BOTTOM the one
+ *         with the larger -- and (c_b, a_b) the other; t = (z - c_a) / (c_b - c_a), one IEEE division; y = a_a + t * (a_b - a_a), the
+ *         product rounded, then added, no fused multiply-add.  A neighbour of zero thickness takes part with its own midpoint; a zero
+ *         denominator gives what IEEE gives.
+ *     missing: any double, NaN included.
+ *     Every value is a fixed sequence of IEEE operations on the column's own data: a host reproduces it to the bit from samsim_get_state.
+ *   samsim_set_sensors.  n in 1..SAMSIM_MAX_SENSORS stores the specs and allocates the score rows [SAMSIM_NSF][ncol] as doubles on the
+ *     device (64-bit offsets), all 0.0.  n == 0 with NULL removes sensors and rows (also when none was set).  A call that is refused
+ *     leaves the previous sensors and rows in force.  Sensors and rows belong to the caller, as labels and tracks do: they are not
+ *     part of a checkpoint; samsim_set_state, samsim_set_status, samsim_set_clock and stepping leave them alone; samsim_destroy frees
+ *     them.
+ *   samsim_get_sensor_values.  y[i][j] = the value of sensor i for column cols[j], y being [n][ncols].  The list rules are those of
+ *     samsim_get_columns: ncols in 1..SAMSIM_SELECT_MAX_OUT, every index checked on the host first, any order, duplicates allowed.
+ *     It writes nothing to the ensemble or to the rows.
+ *   samsim_score.  A column is SCORED if its status is 0 and, with group >= 0, its label (samsim_set_groups) equals group; group == -1
+ *     needs no labels.  For every other column no byte of any score row changes.  Sensor i is VALID for a scored column if and only if
+ *     obs[i] is not a NaN and the sensor is in the ice; a NaN y_i of a valid sensor is not filtered (it makes J a NaN, which is
+ *     information).  w_i = weight[i], or 1.0 when weight is NULL.  From N = J = B = W = 0.0, over the valid sensors in ascending i:
+ *       d = y_i - obs[i];  N = N + 1;  J = J + w_i * (d * d) (d * d rounded, then the product with w_i rounded, then added);
+ *       B = B + w_i * d;  W = W + w_i.
+ *     Then, in this order: N_LAST, J_LAST, B_LAST, W_LAST = N, J, B, W; and if N > 0: N_SUM += N, J_SUM += J, B_SUM += B, W_SUM += W,
+ *     CALLS += 1.  The RMS misfit sqrt(J_SUM / W_SUM) and the bias B_SUM / W_SUM are formed on the host.  No cross-lane arithmetic, no
+ *     atomics: two calls on equal states give equal bytes, and a column's bytes do not depend on its neighbours.  One observation
+ *     vector per call; a multi-site ensemble is scored site by site through `group`.
+ *   samsim_get_scores / samsim_set_score_state.  The window [col0, col0 + ncols) of the nine rows, [SAMSIM_NSF][ncols], out of the
+ *     handle and back into one (a restart, as samsim_get_tracks / samsim_set_track_state).  samsim_reset_scores sets every row to 0.0.
+ *   Slots.  SAMSIM_SCORE_SLOT(field), field an enum samsim_score_field, is accepted wherever a slot is while sensors are set --
+ *     samsim_get_ensemble_stats, samsim_get_group_stats, samsim_get_histogram, the slots of samsim_get_covariance, predictor_slot of
+ *     samsim_get_profile_regression, the terms of samsim_select_columns -- and resolves to that row; without sensors, or with
+ *     field >= SAMSIM_NSF, it is the SAMSIM_ERR_ARG of any bad slot.  There is no dirty flag: the rows change only in samsim_score,
+ *     samsim_set_score_state and samsim_reset_scores.
+ *   Not in scope.  The tracks do not take a sensor or a score as an observable (enum samsim_observable_kind is closed); sensors in the
+ *     snow, the air or the ocean are simply not in the ice; tracers are not arrays of this call; one observation vector per call.
+ *   Errors, all found before any device work, in this order; a call that is refused writes nothing to the caller's buffers or to the
+ *     rows.  samsim_set_sensors: SAMSIM_ERR_ARG for h NULL; n outside 0..SAMSIM_MAX_SENSORS; specs NULL with n > 0 (or not NULL with
+ *     n == 0); then per spec in order: SAMSIM_ERR_ABI for a wrong struct_size; SAMSIM_ERR_ARG for a bad kind; a bad id for the kind; a
+ *     bad origin or interp; a non-zero id, origin, interp or z where the kind takes none; a non-finite or negative z; reserved != 0.
+ *     SAMSIM_ERR_NOMEM if the rows cannot be allocated (the previous ones stay).  samsim_score: SAMSIM_ERR_ARG for h or obs NULL; no
+ *     sensors set; a weight that is not finite or not > 0 in a position where obs is not a NaN; the group checks of
+ *     samsim_get_covariance.  The others: SAMSIM_ERR_ARG for NULL pointers; no sensors set; a window outside [0, ncol); the list checks
+ *     of samsim_get_columns. */
+#define SAMSIM_MAX_SENSORS 32
+#define SAMSIM_SCORE_SLOT(field) (0x30000 + (field))
+enum samsim_sensor_kind { SAMSIM_SENSOR_PROFILE = 0, SAMSIM_SENSOR_SCALAR, SAMSIM_SENSOR_ICE_THICKNESS, SAMSIM_NSENSOR_KINDS };
+enum samsim_sensor_interp { SAMSIM_SENSOR_STEP = 0, SAMSIM_SENSOR_LINEAR = 1 };
+enum samsim_score_field {
+  SAMSIM_SF_N_LAST = 0, SAMSIM_SF_J_LAST, SAMSIM_SF_B_LAST, SAMSIM_SF_W_LAST,
+  SAMSIM_SF_N_SUM, SAMSIM_SF_J_SUM, SAMSIM_SF_B_SUM, SAMSIM_SF_W_SUM, SAMSIM_SF_CALLS, SAMSIM_NSF };
+typedef struct samsim_sensor_spec {   /* 40 bytes */
+  int32_t struct_size, kind, id, origin, interp, reserved;
+  double  z, missing;
+} samsim_sensor_spec;
+int samsim_set_sensors(samsim_handle *h, int32_t n, const samsim_sensor_spec *specs);
+int samsim_get_sensor_values(samsim_handle *h, int64_t ncols, const int64_t *cols, double *y /*[n][ncols]*/);
+int samsim_score(samsim_handle *h, const double *obs /*[n]*/, const double *weight /*[n] or NULL*/, int32_t group);
+int samsim_get_scores(samsim_handle *h, int64_t col0, int64_t ncols, double *out /*[SAMSIM_NSF][ncols]*/);
+int samsim_set_score_state(samsim_handle *h, int64_t col0, int64_t ncols, const double *in /*[SAMSIM_NSF][ncols]*/);
+int samsim_reset_scores(samsim_handle *h);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

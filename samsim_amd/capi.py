@@ -197,8 +197,47 @@ def func_slot(i) -> int:
     return 0x20000 + int(i)
 
 
+MAX_SENSORS = 32            # SAMSIM_MAX_SENSORS
+# enum samsim_sensor_kind, enum samsim_sensor_interp, enum samsim_score_field
+SENSOR_KINDS = ["profile", "scalar", "ice_thickness"]
+SK = {n: i for i, n in enumerate(SENSOR_KINDS)}
+SENSOR_INTERPS = {"step": 0, "linear": 1}
+SCORE_FIELDS = ["N_LAST", "J_LAST", "B_LAST", "W_LAST", "N_SUM", "J_SUM", "B_SUM", "W_SUM", "CALLS"]
+SF = {n: i for i, n in enumerate(SCORE_FIELDS)}
+NSF = len(SCORE_FIELDS)
+
+
+class SensorSpec(C.Structure):
+    """samsim_sensor_spec: the model's equivalent of one sensor, per column: a layer array at depth z from `origin` ("profile", by
+    "step" or "linear" between layer midpoints), a stored column scalar ("scalar"), or the current ice thickness ("ice_thickness");
+    `missing` is the value of a profile sensor that is not in the ice"""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("id", C.c_int32), ("origin", C.c_int32), ("interp", C.c_int32),
+                ("reserved", C.c_int32), ("z", C.c_double), ("missing", C.c_double)]
+
+    @staticmethod
+    def make(kind, name=None, z=0.0, origin="top", interp="step", missing=np.nan) -> "SensorSpec":
+        """kind from SENSOR_KINDS; name from ARRAYS ("profile") or SCALARS ("scalar"), or its number; origin from PROFILE_ORIGINS,
+        interp from SENSOR_INTERPS (names or their numbers)"""
+        k = SK[kind] if isinstance(kind, str) else int(kind)
+        if name is None:
+            i = 0
+        elif isinstance(name, str):
+            i = S[name] if k == SK["scalar"] else A[name]
+        else:
+            i = int(name)
+        o = PROFILE_ORIGINS[origin] if isinstance(origin, str) else int(origin)
+        p = SENSOR_INTERPS[interp] if isinstance(interp, str) else int(interp)
+        return SensorSpec(C.sizeof(SensorSpec), k, i, o, p, 0, float(z), float(missing))
+
+
+def score_slot(field) -> int:
+    """SAMSIM_SCORE_SLOT(field): a row of the per-column misfit (field from SCORE_FIELDS or its number) as a slot of ensemble_stats,
+    group_stats, histogram, covariance, profile_regression and select, while sensors are set"""
+    return 0x30000 + (SF[field] if isinstance(field, str) else int(field))
+
+
 def _slot(name) -> int:
-    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot or func_slot gives it"""
+    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot, func_slot or score_slot gives it"""
     if isinstance(name, (int, np.integer)):
         return int(name)
     return -1 if name == "N_active" else S[name]
@@ -450,6 +489,14 @@ class Solver:
         # and the column functionals
         func_sig = {"set_functionals": [vp, C.c_int32, C.POINTER(FunctionalSpec)], "get_functionals": [vp, C.c_int32, i64, i64, C.c_void_p]}
         for n, a in func_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the sensors and scores
+        sensor_sig = {"set_sensors": [vp, C.c_int32, C.POINTER(SensorSpec)], "get_sensor_values": [vp, i64, C.c_void_p, C.c_void_p],
+                      "score": [vp, C.c_void_p, C.c_void_p, C.c_int32], "get_scores": [vp, i64, i64, C.c_void_p],
+                      "set_score_state": [vp, i64, i64, C.c_void_p], "reset_scores": [vp]}
+        for n, a in sensor_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -839,6 +886,55 @@ class Solver:
         buf = np.zeros(max(0, n))
         self._chk(self._f("get_functionals")(self._h, int(index), col0, n, buf.ctypes.data), "get_functionals")
         return buf
+
+    # -- sensors and the per-column misfit
+    def set_sensors_raw(self, n, specs):
+        """samsim_set_sensors with the arguments as given (no checks on this side): specs a ctypes array of SensorSpec or None"""
+        self._chk(self._f("set_sensors")(self._h, int(n), specs), "set_sensors")
+        self.nsensors = int(n) if specs is not None else 0
+
+    def set_sensors(self, specs):
+        """name the sensors `specs` (SensorSpec, at most MAX_SENSORS) and allocate the score rows, all zero (samsim_set_sensors):
+        score_slot(field) is then a row wherever a slot is accepted.  set_sensors(None) removes sensors and rows"""
+        if specs is None:
+            return self.set_sensors_raw(0, None)
+        specs = list(specs)
+        self.set_sensors_raw(len(specs), (SensorSpec * max(1, len(specs)))(*specs))
+
+    def sensor_values(self, cols) -> np.ndarray:
+        """float64 [nsensors, len(cols)]: the model's equivalent of every sensor for the columns `cols` (any order, duplicates
+        allowed, at most SELECT_MAX_OUT), stopped ones included (samsim_get_sensor_values)"""
+        cols = np.ascontiguousarray(cols, dtype=np.int64)
+        assert cols.ndim == 1
+        y = np.zeros((getattr(self, "nsensors", 0), cols.size))
+        self._chk(self._f("get_sensor_values")(self._h, cols.size, cols.ctypes.data, y.ctypes.data), "get_sensor_values")
+        return y
+
+    def score(self, obs, weight=None, group=None):
+        """add the weighted squared differences between the sensors and the observations `obs` [nsensors] (NaN: no observation) to
+        the score rows of the running columns -- with group: of those with that label of set_groups -- (samsim_score)"""
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        assert obs.shape == (self.nsensors,) and (w is None or w.shape == obs.shape)
+        self._chk(self._f("score")(self._h, obs.ctypes.data, None if w is None else w.ctypes.data, -1 if group is None else int(group)),
+                  "score")
+
+    def scores(self, col0: int = 0, ncols: int | None = None):
+        """{field: float64 [ncols]} of the score rows, fields from SCORE_FIELDS (samsim_get_scores)"""
+        n = self.ncol - col0 if ncols is None else ncols
+        buf = np.zeros((NSF, max(0, n)))
+        self._chk(self._f("get_scores")(self._h, col0, n, buf.ctypes.data), "get_scores")
+        return {f: buf[i] for i, f in enumerate(SCORE_FIELDS)}
+
+    def set_score_state(self, fields, col0: int = 0):
+        """restart: put back what scores() returned for the columns [col0, col0 + ncols) (samsim_set_score_state); set_sensors
+        comes first"""
+        buf = np.ascontiguousarray(np.stack([np.asarray(fields[f], dtype=np.float64) for f in SCORE_FIELDS]))
+        self._chk(self._f("set_score_state")(self._h, col0, buf.shape[1], buf.ctypes.data), "set_score_state")
+
+    def reset_scores(self):
+        """every score row back to 0.0 (samsim_reset_scores)"""
+        self._chk(self._f("reset_scores")(self._h), "reset_scores")
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

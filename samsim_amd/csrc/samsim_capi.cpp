@@ -19,6 +19,7 @@
 #include "samsim_groups.h"
 #include "samsim_hist.h"
 #include "samsim_select.h"
+#include "samsim_sensors.h"
 #include "samsim_sens.h"
 #include "samsim_tracks.h"
 
@@ -85,6 +86,9 @@ struct samsim_handle {
   int32_t nfunc = 0;           // 0: no functionals
   bool func_dirty = true;      // the state changed since the rows were evaluated (stepping, set_state, set_status, set_functionals)
   samsim_functional_spec func[SAMSIM_MAX_FUNCTIONALS]{};
+  double *score_rows = nullptr; // [SAMSIM_NSF][ncol] rows of the per-column misfit (samsim_set_sensors), updated by samsim_score
+  int32_t nsensors = 0;        // 0: no sensors
+  samsim_sensor_spec sensor[SAMSIM_MAX_SENSORS]{};
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -422,11 +426,13 @@ int launch(samsim_handle *h, long long nsteps) {
 }
 
 // a slot of the statistics: an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE, SAMSIM_TRACK_SLOT(track, field) of the tracks in force, or
-// SAMSIM_FUNC_SLOT(i) of the functionals in force
-bool func_slot(int32_t slot) { return slot >= SAMSIM_FUNC_SLOT(0); }
+// SAMSIM_FUNC_SLOT(i) of the functionals in force, or SAMSIM_SCORE_SLOT(field) while sensors are set
+bool func_slot(int32_t slot) { return slot >= SAMSIM_FUNC_SLOT(0) && slot < SAMSIM_FUNC_SLOT(SAMSIM_MAX_FUNCTIONALS); }
+bool score_slot(int32_t slot) { return slot >= SAMSIM_SCORE_SLOT(0) && slot < SAMSIM_SCORE_SLOT(SAMSIM_NSF); }
 bool good_slot(const samsim_handle *h, int32_t slot) {
   if (slot == SAMSIM_STAT_N_ACTIVE || (slot >= 0 && slot < SAMSIM_NSCAL)) return true;
   if (func_slot(slot)) return h->func_rows && slot - SAMSIM_FUNC_SLOT(0) < h->nfunc;
+  if (score_slot(slot)) return h->score_rows != nullptr;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks && o >= 0 && o / 32 < h->ntracks && o % 32 < SAMSIM_NTF;
 }
@@ -435,6 +441,7 @@ const double *slot_row(const samsim_handle *h, int32_t slot) {
   if (slot == SAMSIM_STAT_N_ACTIVE) return nullptr;
   if (slot < SAMSIM_NSCAL) return h->scal + (size_t)slot * (size_t)h->ncol;
   if (func_slot(slot)) return h->func_rows + (size_t)(slot - SAMSIM_FUNC_SLOT(0)) * (size_t)h->ncol;
+  if (score_slot(slot)) return h->score_rows + (size_t)(slot - SAMSIM_SCORE_SLOT(0)) * (size_t)h->ncol;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks + ((size_t)(o / 32) * SAMSIM_NTF + (size_t)(o % 32)) * (size_t)h->ncol;
 }
@@ -605,6 +612,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->spec); (void)hipFree(h->flags); (void)hipFree(h->d_stat); (void)hipFree(h->d_prof); (void)hipFree(h->stage);
   (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens); (void)hipFree(h->tracks);
   (void)hipFree(h->func_rows);
+  (void)hipFree(h->score_rows);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -1517,6 +1525,197 @@ int samsim_get_functionals(samsim_handle *h, int32_t index, int64_t col0, int64_
   HIPCHK(hipStreamSynchronize(h->stream));
   if (ncols == 0) return SAMSIM_OK;
   HIPCHK(hipMemcpy(out, h->func_rows + (size_t)index * (size_t)h->ncol + (size_t)col0, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+// the checks of one sensor, in the order samsim.h gives
+static int check_sensor_spec(const samsim_sensor_spec &s) {
+  if (s.struct_size != (int32_t)sizeof(samsim_sensor_spec)) return SAMSIM_ERR_ABI;
+  switch (s.kind) {
+    case SAMSIM_SENSOR_PROFILE: if (s.id < 0 || s.id >= SAMSIM_NARR) return SAMSIM_ERR_ARG; break;
+    case SAMSIM_SENSOR_SCALAR: if (s.id < 0 || s.id >= SAMSIM_NSCAL) return SAMSIM_ERR_ARG; break;
+    case SAMSIM_SENSOR_ICE_THICKNESS: if (s.id != 0) return SAMSIM_ERR_ARG; break;
+    default: return SAMSIM_ERR_ARG;
+  }
+  if (s.origin != SAMSIM_PROFILE_FROM_TOP && s.origin != SAMSIM_PROFILE_FROM_BOTTOM) return SAMSIM_ERR_ARG;
+  if (s.interp != SAMSIM_SENSOR_STEP && s.interp != SAMSIM_SENSOR_LINEAR) return SAMSIM_ERR_ARG;
+  if (s.kind != SAMSIM_SENSOR_PROFILE && (s.origin != 0 || s.interp != 0 || !(s.z == 0.0))) return SAMSIM_ERR_ARG;
+  if (!std::isfinite(s.z) || s.z < 0.0) return SAMSIM_ERR_ARG;
+  if (s.reserved != 0) return SAMSIM_ERR_ARG;
+  return SAMSIM_OK;
+}
+
+// The walks of one evaluation: the distinct rows each profile sensor needs -- its array; S_abs and m for S_bu once the kernel has run,
+// as samsim_get_state then forms the quotient -- are deduplicated and the sensors put into groups of at most DEV_SENSOR_GROUP_ROWS
+// rows: a sensor joins the first group in which the union of the rows still fits, else it begins a new one.
+static void sensor_plan(const samsim_handle *h, SensorParams *p) {
+  int ng = 0;
+  for (int i = 0; i < h->nsensors; ++i) {
+    const samsim_sensor_spec &s = h->sensor[i];
+    SensorDev &d = p->s[i];
+    d = SensorDev{s.kind, s.id, s.origin, s.interp, DEV_SENSOR_PLAIN, -1, 0, 0, s.z, s.missing};
+    if (s.kind == SAMSIM_SENSOR_ICE_THICKNESS) p->need_H = 1;
+    if (s.kind != SAMSIM_SENSOR_PROFILE) continue;
+    if (s.origin == SAMSIM_PROFILE_FROM_BOTTOM) p->need_H = 1;
+    int need[2] = {s.id, -1};
+    if (s.id == SAMSIM_A_S_ABS) d.mode = DEV_SENSOR_S_ABS;
+    if (s.id == SAMSIM_A_S_BU && h->stepped) { d.mode = DEV_SENSOR_S_BU; need[0] = SAMSIM_A_S_ABS; need[1] = SAMSIM_A_M; }
+    auto find = [&](int g, int a) { for (int j = 0; j < p->gn[g]; ++j) if (p->grow[g][j] == a) return j; return -1; };
+    int g = 0;
+    for (; g < ng; ++g) {
+      int missing = 0;
+      for (int a : need) if (a >= 0 && find(g, a) < 0) ++missing;
+      if (p->gn[g] + missing <= DEV_SENSOR_GROUP_ROWS) break;
+    }
+    if (g == ng) p->gn[ng++] = 0;
+    int at[2] = {0, 0};
+    for (int j = 0; j < 2; ++j) {
+      if (need[j] < 0) continue;
+      at[j] = find(g, need[j]);
+      if (at[j] < 0) { at[j] = p->gn[g]; p->grow[g][p->gn[g]++] = (int8_t)need[j]; }
+    }
+    d.group = g; d.ia = at[0]; d.ib = at[1];
+  }
+  p->ngroups = ng;
+}
+
+// what a score and the values of a list share
+static void sensor_params(const samsim_handle *h, SensorParams *p) {
+  p->lay = h->lay; p->scal = h->scal; p->n_active = h->n_active; p->status = h->status; p->flags = h->flags;
+  p->ncol = h->ncol; p->N = h->cfg.nlayer; p->ns = h->nsensors; p->stepped = h->stepped ? 1 : 0;
+  p->group = -1;
+  sensor_plan(h, p);
+}
+
+static hipError_t zero_scores(samsim_handle *h, double *rows) {
+  return fill(rows, (size_t)SAMSIM_NSF * (size_t)h->ncol, 0.0, h->stream);
+}
+
+int samsim_set_sensors(samsim_handle *h, int32_t n, const samsim_sensor_spec *specs) {
+  // every check first: a call that is refused leaves the previous sensors and rows in force
+  if (!h) return SAMSIM_ERR_ARG;
+  if (n < 0 || n > SAMSIM_MAX_SENSORS) return SAMSIM_ERR_ARG;
+  if ((n > 0 && !specs) || (n == 0 && specs)) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < n; ++i) {
+    const int rc = check_sensor_spec(specs[i]);
+    if (rc) return rc;
+  }
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the new rows hold their zeros on the device before the handle sees them
+  double *rows = nullptr;
+  if (n > 0) {
+    if (dalloc(&rows, (size_t)SAMSIM_NSF * (size_t)h->ncol) != hipSuccess) {
+      (void)hipGetLastError();
+      return SAMSIM_ERR_NOMEM;
+    }
+    if (!hip_ok(zero_scores(h, rows), "fill scores") || !hip_ok(hipStreamSynchronize(h->stream), "sync")) {
+      (void)hipFree(rows);
+      return SAMSIM_ERR_HIP;
+    }
+  }
+  (void)hipFree(h->score_rows);
+  h->score_rows = rows;
+  h->nsensors = n;
+  static_assert(sizeof(samsim_sensor_spec) == 40, "samsim_sensor_spec of samsim.h");
+  for (int i = 0; i < n; ++i) h->sensor[i] = specs[i];
+  return SAMSIM_OK;
+}
+
+int samsim_get_sensor_values(samsim_handle *h, int64_t ncols, const int64_t *cols, double *y) {
+  // every check first: a call that is refused writes nothing to the caller's buffer
+  if (!h || !cols || !y) return SAMSIM_ERR_ARG;
+  if (!h->score_rows) return SAMSIM_ERR_ARG;
+  if (ncols < 1 || ncols > SAMSIM_SELECT_MAX_OUT) return SAMSIM_ERR_ARG;
+  for (int64_t j = 0; j < ncols; ++j)
+    if (cols[j] < 0 || cols[j] >= h->ncol) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
+  long long *d_cols = (long long *)((char *)h->d_select + DEV_SEL_LIST_AT);
+  const size_t w = (size_t)ncols, ns = (size_t)h->nsensors;
+  HIPCHK(stage_for(h, ns * (w < DEV_SENSOR_PIECE ? w : (size_t)DEV_SENSOR_PIECE)));
+  HIPCHK(hipMemcpyAsync(d_cols, cols, sizeof(int64_t) * w, hipMemcpyHostToDevice, h->stream));
+  SensorParams p{};
+  sensor_params(h, &p);
+  p.out = h->stage;
+  // the list's positions in pieces of DEV_SENSOR_PIECE: the scratch holds [n][piece] values, whatever the list
+  for (size_t p0 = 0; p0 < w; p0 += DEV_SENSOR_PIECE) {
+    const size_t pw = w - p0 < DEV_SENSOR_PIECE ? w - p0 : (size_t)DEV_SENSOR_PIECE;
+    p.cols = d_cols + p0;
+    p.npos = (long long)pw;
+    HIPCHK(samsim_launch_sensor_values(&p, h->stream));
+    HIPCHK(copy_rows(y + p0, w, h->stage, pw, pw, ns, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return SAMSIM_OK;
+}
+
+int samsim_score(samsim_handle *h, const double *obs, const double *weight, int32_t group) {
+  if (!h || !obs) return SAMSIM_ERR_ARG;
+  if (!h->score_rows) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < h->nsensors; ++i)
+    if (weight && !std::isnan(obs[i]) && !(std::isfinite(weight[i]) && weight[i] > 0.0)) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  SensorParams p{};
+  sensor_params(h, &p);
+  p.out = h->score_rows;
+  p.labels = group >= 0 ? h->groups : nullptr;
+  p.group = group;
+  for (int i = 0; i < h->nsensors; ++i) {
+    const bool have = !std::isnan(obs[i]);
+    if (have) p.obs_mask |= 1u << i;
+    p.obs[i] = have ? obs[i] : 0.0;
+    p.weight[i] = (weight && have) ? weight[i] : 1.0;
+  }
+  HIPCHK(samsim_launch_score(&p, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+// the checks samsim_get_scores and samsim_set_score_state share, in the order samsim.h gives
+static int check_score_window(const samsim_handle *h, const void *buf, int64_t col0, int64_t ncols) {
+  if (!h || !buf) return SAMSIM_ERR_ARG;
+  if (!h->score_rows) return SAMSIM_ERR_ARG;
+  if (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) return SAMSIM_ERR_ARG;
+  return SAMSIM_OK;
+}
+
+int samsim_get_scores(samsim_handle *h, int64_t col0, int64_t ncols, double *out) {
+  int rc = check_score_window(h, out, col0, ncols);
+  if (rc) return rc;
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  const size_t nc = (size_t)h->ncol, w = (size_t)ncols;
+  HIPCHK(hipMemcpy2D(out, w * sizeof(double), h->score_rows + (size_t)col0, nc * sizeof(double), w * sizeof(double), (size_t)SAMSIM_NSF,
+                     hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+int samsim_set_score_state(samsim_handle *h, int64_t col0, int64_t ncols, const double *in) {
+  int rc = check_score_window(h, in, col0, ncols);
+  if (rc) return rc;
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  const size_t nc = (size_t)h->ncol, w = (size_t)ncols;
+  HIPCHK(hipMemcpy2D(h->score_rows + (size_t)col0, nc * sizeof(double), in, w * sizeof(double), w * sizeof(double), (size_t)SAMSIM_NSF,
+                     hipMemcpyHostToDevice));
+  return SAMSIM_OK;
+}
+
+int samsim_reset_scores(samsim_handle *h) {
+  if (!h || !h->score_rows) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(zero_scores(h, h->score_rows));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }
 
