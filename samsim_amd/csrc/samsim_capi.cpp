@@ -258,13 +258,14 @@ __global__ void fill_i32(int32_t *dst, size_t n, int32_t v) {
 
 // S_bu(k) = S_abs(k)/m(k) for the active layers: the kernel keeps the bulk salinity in registers only (every reader
 // derives it from S_abs and m), so the array is brought up to date when the host asks for the state
-__global__ void refresh_s_bu(double *lay, const int32_t *n_active, const int32_t *status, size_t ncol, int N, size_t col0, size_t w) {
+__global__ void refresh_s_bu(double *lay, const int32_t *n_active, const int32_t *status, const int32_t *flags, size_t ncol, int N, size_t col0,
+                             size_t w) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= w) return;
   const size_t c = col0 + i;
-  if (status[c]) return;   // a column that stopped keeps what it held (its masses may be zero)
-  const int na = n_active[c];
-  for (int k = 0; k < na; ++k) {
+  const column_read::Column q = column_read::column(n_active, status, flags, c, N, true);
+  if (!q.adjust) return;   // a column that stopped keeps what it held (its masses may be zero)
+  for (int k = 0; k < q.na; ++k) {
     const double m = lay[DEV_LAY_INDEX(SAMSIM_A_M, k, c, N, ncol)];
     if (m != 0.0) lay[DEV_LAY_INDEX(SAMSIM_A_S_BU, k, c, N, ncol)] = lay[DEV_LAY_INDEX(SAMSIM_A_S_ABS, k, c, N, ncol)] / m;
   }
@@ -273,15 +274,16 @@ __global__ void refresh_s_bu(double *lay, const int32_t *n_active, const int32_t
 // The health check at the end of a step clamps S_abs >= 0 over the active layers (mo_grotz.f90:812-818); the step kernel applies it
 // in the first sweep of the NEXT step.  samsim_get_state applies it to what it returns (and to the device copy, which the next first
 // sweep would clamp to the same values), so the state at a step boundary is the reference's and a checkpoint holds nothing that still
-// waits for the clamp.  Columns that stopped, and columns uploaded since the last step (COLF_RESTART), keep what they hold.
+// waits for the clamp.  Columns that stopped, and columns uploaded since the last step (COLF_RESTART), keep what they hold
+// (column_read::Column; both kernels are launched only once the step kernel has run).
 __global__ void clamp_s_abs(double *lay, const int32_t *n_active, const int32_t *status, const int32_t *flags, size_t ncol, int N, size_t col0,
                             size_t w) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= w) return;
   const size_t c = col0 + i;
-  if (status[c] || (flags[c] & COLF_RESTART)) return;
-  const int na = n_active[c];
-  for (int k = 0; k < na; ++k) {
+  const column_read::Column q = column_read::column(n_active, status, flags, c, N, true);
+  if (!q.clamp) return;
+  for (int k = 0; k < q.na; ++k) {
     const size_t j = DEV_LAY_INDEX(SAMSIM_A_S_ABS, k, c, N, ncol);
     if (lay[j] < 0.0) lay[j] = 0.0;
   }
@@ -458,33 +460,40 @@ int use(samsim_handle *h, bool stepping = false) {
   return SAMSIM_OK;
 }
 
-// The walks of one evaluation: the distinct rows each functional needs -- its array; S_abs and m for S_bu once the kernel has run, as
-// samsim_get_state then forms the quotient -- are deduplicated and the functionals put into groups of at most DEV_FUNC_GROUP_ROWS rows,
-// in their order: a functional joins the current group if the union of the rows still fits, else it begins the next.
+// The rows an item on `array` needs and how its layer value is formed from them (column_read::layer_mode): its array; S_abs and m for
+// S_bu once the kernel has run, as samsim_get_state then forms the quotient.  row_plan_place (samsim_row_plan.h) puts it into a walk.
+template <int MAXG>
+RowPlace plan_item(RowPlan<MAXG> &plan, int array, bool stepped, int32_t *mode) {
+  *mode = array == SAMSIM_A_S_ABS ? column_read::LAYER_S_ABS : column_read::LAYER_PLAIN;
+  if (array != SAMSIM_A_S_BU || !stepped) return row_plan_place(plan, array, -1);
+  *mode = column_read::LAYER_S_BU;
+  return row_plan_place(plan, SAMSIM_A_S_ABS, SAMSIM_A_M);
+}
+
+// func_plan and sensor_plan fill a Params struct that arrives zeroed (`FuncParams p{}`, `SensorParams p{}`): the plan starts from no
+// group, and it has room for one group per item (nfunc <= SAMSIM_MAX_FUNCTIONALS, nsensors <= SAMSIM_MAX_SENSORS).
 void func_plan(const samsim_handle *h, FuncParams *p) {
-  int g = 0;
-  p->gn[0] = 0;
   for (int i = 0; i < h->nfunc; ++i) {
     const samsim_functional_spec &s = h->func[i];
     FuncDev &d = p->f[i];
-    d = FuncDev{s.kind, s.origin, s.sense, DEV_FUNC_PLAIN, 0, 0, 0, 0, s.z_lo, s.z_hi, s.threshold, s.missing};
-    int need[2] = {s.array, -1};
-    if (s.array == SAMSIM_A_S_ABS) d.mode = DEV_FUNC_S_ABS;
-    if (s.array == SAMSIM_A_S_BU && h->stepped) { d.mode = DEV_FUNC_S_BU; need[0] = SAMSIM_A_S_ABS; need[1] = SAMSIM_A_M; }
-    auto find = [&](int a) { for (int j = 0; j < p->gn[g]; ++j) if (p->grow[g][j] == a) return j; return -1; };
-    int missing = 0;
-    for (int a : need) if (a >= 0 && find(a) < 0) ++missing;
-    if (p->gn[g] + missing > DEV_FUNC_GROUP_ROWS) p->gn[++g] = 0;
-    int at[2] = {0, 0};
-    for (int j = 0; j < 2; ++j) {
-      if (need[j] < 0) continue;
-      at[j] = find(need[j]);
-      if (at[j] < 0) { at[j] = p->gn[g]; p->grow[g][p->gn[g]++] = need[j]; }
-    }
-    d.group = g; d.ia = at[0]; d.ib = at[1];
+    d = FuncDev{s.kind, s.origin, s.sense, 0, 0, 0, 0, 0, s.z_lo, s.z_hi, s.threshold, s.missing};
+    const RowPlace at = plan_item(p->plan, s.array, h->stepped, &d.mode);
+    d.group = at.group; d.ia = at.ia; d.ib = at.ib;
     if (s.origin == SAMSIM_PROFILE_FROM_BOTTOM) p->need_H = 1;
   }
-  p->ngroups = g + 1;
+}
+
+void sensor_plan(const samsim_handle *h, SensorParams *p) {
+  for (int i = 0; i < h->nsensors; ++i) {
+    const samsim_sensor_spec &s = h->sensor[i];
+    SensorDev &d = p->s[i];
+    d = SensorDev{s.kind, s.id, s.origin, s.interp, 0, -1, 0, 0, s.z, s.missing};
+    if (s.kind == SAMSIM_SENSOR_ICE_THICKNESS) p->need_H = 1;
+    if (s.kind != SAMSIM_SENSOR_PROFILE) continue;
+    if (s.origin == SAMSIM_PROFILE_FROM_BOTTOM) p->need_H = 1;
+    const RowPlace at = plan_item(p->plan, s.id, h->stepped, &d.mode);
+    d.group = at.group; d.ia = at.ia; d.ib = at.ib;
+  }
 }
 
 // the rows of the functionals brought up to date, on the handle's first stream: one kernel, and only when the state changed since the
@@ -749,7 +758,7 @@ int samsim_get_state(samsim_handle *h, samsim_state_soa *s, int64_t col0) {
     HIPCHK(hipGetLastError());
   }
   if (s->narr == SAMSIM_NARR && h->stepped) {
-    hipLaunchKernelGGL(refresh_s_bu, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, h->stream, h->lay, h->n_active, h->status,
+    hipLaunchKernelGGL(refresh_s_bu, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, h->stream, h->lay, h->n_active, h->status, h->flags,
                        nc, (int)N, (size_t)col0, w);
     HIPCHK(hipGetLastError());
   }
@@ -1348,13 +1357,17 @@ int samsim_reset_tracks(samsim_handle *h) {
   return SAMSIM_OK;
 }
 
+// a window [col0, col0 + ncols) of the handle's columns, which may be empty and may begin at ncol
+static int check_window(const samsim_handle *h, int64_t col0, int64_t ncols) {
+  return (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) ? SAMSIM_ERR_ARG : SAMSIM_OK;
+}
+
 // the checks samsim_get_tracks and samsim_set_track_state share, in the order samsim.h gives
 static int check_track_window(const samsim_handle *h, const void *buf, int32_t track, int64_t col0, int64_t ncols) {
   if (!h || !buf) return SAMSIM_ERR_ARG;
   if (!h->tracks) return SAMSIM_ERR_ARG;
   if (track < 0 || track >= h->ntracks) return SAMSIM_ERR_ARG;
-  if (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) return SAMSIM_ERR_ARG;
-  return SAMSIM_OK;
+  return check_window(h, col0, ncols);
 }
 
 int samsim_get_tracks(samsim_handle *h, int32_t track, int64_t col0, int64_t ncols, double *out) {
@@ -1428,6 +1441,19 @@ int samsim_select_columns(samsim_handle *h, const samsim_selection *sel, int64_t
   return SAMSIM_OK;
 }
 
+// A host list of column indices, checked against the handle and -- behind use() -- on its way into the index list of the select
+// scratch, on the handle's stream: *d_cols is the device copy.  A list that is refused touches nothing.
+static int stage_list(samsim_handle *h, int64_t ncols, const int64_t *cols, long long **d_cols) {
+  for (int64_t j = 0; j < ncols; ++j)
+    if (cols[j] < 0 || cols[j] >= h->ncol) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
+  *d_cols = (long long *)((char *)h->d_select + DEV_SEL_LIST_AT);
+  HIPCHK(hipMemcpyAsync(*d_cols, cols, sizeof(int64_t) * (size_t)ncols, hipMemcpyHostToDevice, h->stream));
+  return SAMSIM_OK;
+}
+
 int samsim_get_columns(samsim_handle *h, int64_t ncols, const int64_t *cols, samsim_state_soa *s, int32_t *status, int64_t *step,
                        int32_t *layer) {
   // every check first: a call that is refused writes nothing to the caller's buffers
@@ -1436,19 +1462,14 @@ int samsim_get_columns(samsim_handle *h, int64_t ncols, const int64_t *cols, sam
   if (!s->lay || !s->scal || !s->n_active || s->nlayer != h->cfg.nlayer) return SAMSIM_ERR_ARG;
   if (s->narr != SAMSIM_NPROG && s->narr != SAMSIM_NARR) return SAMSIM_ERR_ARG;
   if (ncols < 1 || ncols > SAMSIM_SELECT_MAX_OUT || s->ncol != ncols) return SAMSIM_ERR_ARG;
-  int rc;
-  for (int64_t j = 0; j < ncols; ++j)
-    if (cols[j] < 0 || cols[j] >= h->ncol) return SAMSIM_ERR_ARG;
-  rc = use(h);
+  long long *d_cols = nullptr;
+  int rc = stage_list(h, ncols, cols, &d_cols);
   if (rc) return rc;
-  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
-  long long *d_cols = (long long *)((char *)h->d_select + DEV_SEL_LIST_AT);
   const size_t N = (size_t)s->nlayer, w = (size_t)ncols;
   // the list's positions in pieces as samsim_get_state cuts a window; the staging buffer also takes the per-column rows, one piece
   const size_t pc = stage_cols(s->narr, N), rows = (size_t)s->narr * N;
   const size_t lay_n = rows * (w < pc ? w : pc), col_n = (w * DEV_SEL_COLUMN_BYTES + 7) / 8;
   HIPCHK(stage_for(h, lay_n > col_n ? lay_n : col_n));
-  HIPCHK(hipMemcpyAsync(d_cols, cols, sizeof(int64_t) * w, hipMemcpyHostToDevice, h->stream));
   HIPCHK(samsim_launch_gather_columns(h->scal, h->n_active, h->status, h->err_step, h->err_layer, d_cols, h->stage, h->ncol, (long long)w,
                                       h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1517,8 +1538,9 @@ int samsim_get_functionals(samsim_handle *h, int32_t index, int64_t col0, int64_
   if (!h || !out) return SAMSIM_ERR_ARG;
   if (!h->func_rows) return SAMSIM_ERR_ARG;
   if (index < 0 || index >= h->nfunc) return SAMSIM_ERR_ARG;
-  if (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) return SAMSIM_ERR_ARG;
-  int rc = use(h);
+  int rc = check_window(h, col0, ncols);
+  if (rc) return rc;
+  rc = use(h);
   if (rc) return rc;
   rc = func_refresh(h);
   if (rc) return rc;
@@ -1543,40 +1565,6 @@ static int check_sensor_spec(const samsim_sensor_spec &s) {
   if (!std::isfinite(s.z) || s.z < 0.0) return SAMSIM_ERR_ARG;
   if (s.reserved != 0) return SAMSIM_ERR_ARG;
   return SAMSIM_OK;
-}
-
-// The walks of one evaluation: the distinct rows each profile sensor needs -- its array; S_abs and m for S_bu once the kernel has run,
-// as samsim_get_state then forms the quotient -- are deduplicated and the sensors put into groups of at most DEV_SENSOR_GROUP_ROWS
-// rows: a sensor joins the first group in which the union of the rows still fits, else it begins a new one.
-static void sensor_plan(const samsim_handle *h, SensorParams *p) {
-  int ng = 0;
-  for (int i = 0; i < h->nsensors; ++i) {
-    const samsim_sensor_spec &s = h->sensor[i];
-    SensorDev &d = p->s[i];
-    d = SensorDev{s.kind, s.id, s.origin, s.interp, DEV_SENSOR_PLAIN, -1, 0, 0, s.z, s.missing};
-    if (s.kind == SAMSIM_SENSOR_ICE_THICKNESS) p->need_H = 1;
-    if (s.kind != SAMSIM_SENSOR_PROFILE) continue;
-    if (s.origin == SAMSIM_PROFILE_FROM_BOTTOM) p->need_H = 1;
-    int need[2] = {s.id, -1};
-    if (s.id == SAMSIM_A_S_ABS) d.mode = DEV_SENSOR_S_ABS;
-    if (s.id == SAMSIM_A_S_BU && h->stepped) { d.mode = DEV_SENSOR_S_BU; need[0] = SAMSIM_A_S_ABS; need[1] = SAMSIM_A_M; }
-    auto find = [&](int g, int a) { for (int j = 0; j < p->gn[g]; ++j) if (p->grow[g][j] == a) return j; return -1; };
-    int g = 0;
-    for (; g < ng; ++g) {
-      int missing = 0;
-      for (int a : need) if (a >= 0 && find(g, a) < 0) ++missing;
-      if (p->gn[g] + missing <= DEV_SENSOR_GROUP_ROWS) break;
-    }
-    if (g == ng) p->gn[ng++] = 0;
-    int at[2] = {0, 0};
-    for (int j = 0; j < 2; ++j) {
-      if (need[j] < 0) continue;
-      at[j] = find(g, need[j]);
-      if (at[j] < 0) { at[j] = p->gn[g]; p->grow[g][p->gn[g]++] = (int8_t)need[j]; }
-    }
-    d.group = g; d.ia = at[0]; d.ib = at[1];
-  }
-  p->ngroups = ng;
 }
 
 // what a score and the values of a list share
@@ -1628,15 +1616,11 @@ int samsim_get_sensor_values(samsim_handle *h, int64_t ncols, const int64_t *col
   if (!h || !cols || !y) return SAMSIM_ERR_ARG;
   if (!h->score_rows) return SAMSIM_ERR_ARG;
   if (ncols < 1 || ncols > SAMSIM_SELECT_MAX_OUT) return SAMSIM_ERR_ARG;
-  for (int64_t j = 0; j < ncols; ++j)
-    if (cols[j] < 0 || cols[j] >= h->ncol) return SAMSIM_ERR_ARG;
-  int rc = use(h);
+  long long *d_cols = nullptr;
+  int rc = stage_list(h, ncols, cols, &d_cols);
   if (rc) return rc;
-  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
-  long long *d_cols = (long long *)((char *)h->d_select + DEV_SEL_LIST_AT);
   const size_t w = (size_t)ncols, ns = (size_t)h->nsensors;
   HIPCHK(stage_for(h, ns * (w < DEV_SENSOR_PIECE ? w : (size_t)DEV_SENSOR_PIECE)));
-  HIPCHK(hipMemcpyAsync(d_cols, cols, sizeof(int64_t) * w, hipMemcpyHostToDevice, h->stream));
   SensorParams p{};
   sensor_params(h, &p);
   p.out = h->stage;
@@ -1680,8 +1664,7 @@ int samsim_score(samsim_handle *h, const double *obs, const double *weight, int3
 static int check_score_window(const samsim_handle *h, const void *buf, int64_t col0, int64_t ncols) {
   if (!h || !buf) return SAMSIM_ERR_ARG;
   if (!h->score_rows) return SAMSIM_ERR_ARG;
-  if (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) return SAMSIM_ERR_ARG;
-  return SAMSIM_OK;
+  return check_window(h, col0, ncols);
 }
 
 int samsim_get_scores(samsim_handle *h, int64_t col0, int64_t ncols, double *out) {

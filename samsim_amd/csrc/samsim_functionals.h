@@ -5,30 +5,21 @@
 
 #include <hip/hip_runtime.h>
 
-#include "samsim_device.h"
+#include "samsim_column_read.h"
+#include "samsim_row_plan.h"
 
-// A walk over the layers serves one group of functionals: those whose arrays need at most DEV_FUNC_GROUP_ROWS distinct rows of the
-// layer block beside thick (S_bu after a step needs two, S_abs and m).  The host deduplicates the rows and forms the groups
-// (func_plan, samsim_capi.cpp); with up to four rows per walk the eight functionals of a handle take one walk in the common case and
-// three at the most.
-#define DEV_FUNC_GROUP_ROWS 4
-#define DEV_FUNC_MAX_GROUPS SAMSIM_MAX_FUNCTIONALS
-
-// how the layer value a_k is formed from the loaded rows
-enum dev_func_mode {
-  DEV_FUNC_PLAIN = 0,   // the stored value of row ia
-  DEV_FUNC_S_ABS,       // row ia is S_abs: the health check's clamp where samsim_get_state applies it
-  DEV_FUNC_S_BU         // row ia is S_abs, row ib is m: the quotient where samsim_get_state forms it, the stored S_bu elsewhere
-};
+// A walk over the layers serves one group of functionals: those whose arrays need at most ROW_PLAN_ROWS distinct rows of the layer
+// block beside thick.  The host forms the groups by first-fit (samsim_row_plan.h; func_plan, samsim_capi.cpp); with up to four rows
+// per walk the eight functionals of a handle take one walk in the common case and three at the most.
 
 // one functional as the kernel sees it: samsim_functional_spec, checked by samsim_set_functionals, and its place in the plan
 struct FuncDev {
   int32_t kind;     // enum samsim_functional_kind
   int32_t origin;   // enum samsim_profile_origin
   int32_t sense;    // +1 (a_k >= threshold), -1 (a_k < threshold), 0
-  int32_t mode;     // enum dev_func_mode
+  int32_t mode;     // enum column_read::layer_mode
   int32_t group;    // the walk that serves it
-  int32_t ia, ib;   // positions among the group's rows; ib only with DEV_FUNC_S_BU
+  int32_t ia, ib;   // positions among the group's rows; ib only with LAYER_S_BU
   int32_t pad;
   double z_lo, z_hi, threshold, missing;
 };
@@ -42,15 +33,12 @@ struct FuncParams {
   long long ncol;
   int32_t N;                  // nlayer
   int32_t nf;
-  int32_t ngroups;
   int32_t stepped;            // the kernel has run: samsim_get_state clamps S_abs and refreshes S_bu in the running columns
   int32_t need_H;             // some functional counts from the bottom: a thick-only pre-pass forms H
-  int32_t pad;
-  int32_t gn[DEV_FUNC_MAX_GROUPS];                        // rows of each group
-  int32_t grow[DEV_FUNC_MAX_GROUPS][DEV_FUNC_GROUP_ROWS]; // their arrays (enum samsim_layer_array)
+  RowPlan<SAMSIM_MAX_FUNCTIONALS> plan;   // the walks: at most one per functional
   FuncDev f[SAMSIM_MAX_FUNCTIONALS];
 };
-static_assert(sizeof(FuncDev) == 64 && sizeof(FuncParams) <= 1024, "the evaluation's parameters travel as a kernel argument");
+static_assert(sizeof(FuncDev) == 64 && sizeof(FuncParams) == 648, "the evaluation's parameters travel as a kernel argument");
 
 // samsim_functionals.hip: enqueues one evaluation of every block of the handle on `stream`
 extern "C" hipError_t samsim_launch_functionals(const FuncParams *p, hipStream_t stream);

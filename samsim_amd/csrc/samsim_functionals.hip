@@ -12,9 +12,8 @@
 // wave maximum of n_active, no atomics, plain division, products rounded before they are added (the Makefile's -ffp-contract=off,
 // and the pragma below for a build that drops it).  Each lane ends with one 8-byte store per functional; nothing else is written.
 //
-// The layer value is what samsim_get_state would return: after a step, in a column that runs, S_abs with the health check's clamp
-// (not in a column uploaded since the last step) and S_bu as S_abs / m where m != 0; the stored values elsewhere.  Clamp and
-// quotient are formed in registers as samsim_tracks.hip forms them.  Every offset into the rows is 64-bit.
+// The layer value is what samsim_get_state would return (samsim_column_read.h), formed in registers.  Every offset into the rows is
+// 64-bit.
 #include <hip/hip_runtime.h>
 
 #include "samsim_functionals.h"
@@ -23,16 +22,10 @@
 
 namespace {
 
+using namespace column_read;
+
 constexpr int kAhead = 4;                            // layers whose rows a wave requests before it waits for the first
-constexpr int kRows = DEV_FUNC_GROUP_ROWS;
-constexpr size_t kRow = DEV_ROWB / sizeof(double);   // doubles from one layer row of a 64-column block to the next
-
-__device__ __forceinline__ int wave_max(int v) {
-  for (int w = 32; w > 0; w >>= 1) { const int o = __shfl_xor(v, w); v = o > v ? o : v; }
-  return v;
-}
-
-__device__ __forceinline__ double ld(const double *p) { return __builtin_nontemporal_load(p); }
+constexpr int kRows = ROW_PLAN_ROWS;
 
 // the running result of one functional in one lane
 struct Acc {
@@ -51,15 +44,7 @@ __device__ __forceinline__ void update(const FuncDev &q, Acc &s, double Z, doubl
   const double xo = e1 - e0;
   if (!(xo > 0.0)) return;   // the layer is not in the window
   const double o = xo;
-  const double xa = q.ia == 0 ? x0 : (q.ia == 1 ? x1 : (q.ia == 2 ? x2 : x3));
-  double a = xa;
-  if (q.mode == DEV_FUNC_S_ABS) {
-    a = (clamp && xa < 0.0) ? 0.0 : xa;
-  } else if (q.mode == DEV_FUNC_S_BU) {
-    const double m = q.ib == 0 ? x0 : (q.ib == 1 ? x1 : (q.ib == 2 ? x2 : x3));
-    if (adjust && m != 0.0) a = ((clamp && xa < 0.0) ? 0.0 : xa) / m;
-    else a = ld(row + SAMSIM_A_S_BU * 64);   // a stopped column, or the rare lane with m = 0: the stored value
-  }
+  const double a = row_value(q.mode, q.ia, q.ib, x0, x1, x2, x3, row, adjust, clamp);
   const bool cond = q.sense > 0 ? a >= q.threshold : (q.sense < 0 ? a < q.threshold : false);
   switch (q.kind) {
     case SAMSIM_FN_INTEGRAL: case SAMSIM_FN_MEAN: {
@@ -99,31 +84,20 @@ __global__ void __launch_bounds__(64) functionals_kernel(const FuncParams p) {
   const long long col = blk * 64 + lane;
   const bool in = col < p.ncol;
   const size_t nc = (size_t)p.ncol, c = (size_t)col;
-  int na = 0;
-  bool adjust = false, clamp = false;
-  if (in) {
-    const int na_raw = p.n_active[c];
-    na = na_raw < 0 ? 0 : (na_raw > p.N ? p.N : na_raw);
-    adjust = p.stepped != 0 && p.status[c] == 0;
-    clamp = adjust && (p.flags[c] & COLF_RESTART) == 0;
-  }
+  Column cl{};
+  if (in) cl = column(p.n_active, p.status, p.flags, c, p.N, p.stepped != 0);
+  const int na = cl.na;
+  const bool adjust = cl.adjust, clamp = cl.clamp;
   const int kmax = wave_max(na);
   // the lane's element of array 0, layer 1; the block is allocated whole, so the lanes beyond ncol read their own (zero) rows
   const double *base = p.lay + DEV_LAY_INDEX(0, 0, (size_t)blk * 64 + lane, p.N, nc);
 
-  double H = 0.0;
-  if (p.need_H) {   // the ice thickness first: Z_k = Z_{k-1} + thick(k), k ascending
-#pragma unroll 4
-    for (int k = 1; k <= kmax; ++k) {
-      const double t = ld(base + (size_t)(k - 1) * kRow + SAMSIM_A_THICK * 64);
-      H = k <= na ? H + t : H;
-    }
-  }
+  const double H = p.need_H ? ice_thickness(base, na, kmax) : 0.0;
 
   Acc acc[SAMSIM_MAX_FUNCTIONALS];
-  for (int g = 0; g < p.ngroups; ++g) {
-    const int gn = p.gn[g];
-    const int o0 = p.grow[g][0] * 64, o1 = p.grow[g][1] * 64, o2 = p.grow[g][2] * 64, o3 = p.grow[g][3] * 64;
+  for (int g = 0; g < p.plan.ngroups; ++g) {
+    const int gn = p.plan.gn[g];
+    const int o0 = p.plan.grow[g][0] * 64, o1 = p.plan.grow[g][1] * 64, o2 = p.plan.grow[g][2] * 64, o3 = p.plan.grow[g][3] * 64;
     double Z = 0.0;
     for (int k0 = 1; k0 <= kmax; k0 += kAhead) {   // the rows of kAhead layers requested together
       double tk[kAhead], x[kRows][kAhead];

@@ -13,12 +13,13 @@
 
 #include <hip/hip_runtime.h>
 
-#include "samsim_device.h"
+#include "samsim_column_read.h"
 
 namespace profile_walk {
 
+using namespace column_read;   // kRow, wave_max, wave_min, ld
+
 constexpr int kAhead = 8;                        // layers whose rows a wave requests before it waits for the first
-constexpr size_t kRow = DEV_ROWB / sizeof(double);   // doubles from one layer row of a 64-column block to the next (samsim_device.h)
 constexpr int kTileStride = DEV_PROF_BINS + 1;   // row stride of the LDS tile in doubles: lane j reads row j without a bank pile-up
 
 // The sink both reductions use: an LDS tile [bin][lane] of the block's values and, per lane, the mask of the bins its column
@@ -33,30 +34,20 @@ struct TileSink {
   }
 };
 
-__device__ __forceinline__ int wave_max(int v) {
-  for (int w = 32; w > 0; w >>= 1) { const int o = __shfl_xor(v, w); v = o > v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-  for (int w = 32; w > 0; w >>= 1) { const int o = __shfl_xor(v, w); v = o < v ? o : v; }
-  return v;
-}
-
-__device__ __forceinline__ double ld(const double *p) { return __builtin_nontemporal_load(p); }
-
 // The value of the requested array in one layer row (`row` = the lane's element of array 0 of that layer) in two halves, so that a
 // wave can request the rows of several layers before it waits for the first: row_request loads the stored value -- for the bulk
-// salinity S_abs and m --, row_value forms a_k from them: S_abs / m where m is not zero (what samsim_get_state returns after a
-// step), the stored S_bu in the rare lane with m = 0.
+// salinity S_abs and m --, requested_value forms a_k from them.  The profile requests read the layer value of
+// samsim_column_read.h with clamp = false and adjust = true, whatever the column: S_abs as stored and S_bu always as the quotient
+// where m != 0 (a stopped column takes no part).  That is their documented definition ("Layer value" of samsim_get_profile_stats,
+// include/samsim.h), kept as it is.
 __device__ __forceinline__ void row_request(const double *row, int array, double &x, double &y) {
   const bool sbu = array == SAMSIM_A_S_BU;
   x = ld(row + (sbu ? (int)SAMSIM_A_S_ABS : array) * 64);
   y = sbu ? ld(row + SAMSIM_A_M * 64) : 1.0;
 }
-__device__ __forceinline__ double row_value(const double *row, int array, double x, double y) {
+__device__ __forceinline__ double requested_value(const double *row, int array, double x, double y) {
   if (array != SAMSIM_A_S_BU) return x;
-  if (y != 0.0) return x / y;
-  return ld(row + SAMSIM_A_S_BU * 64);
+  return s_bu_value(x, y, /*adjust=*/true, /*clamp=*/false, [&] { return ld(row + SAMSIM_A_S_BU * 64); });
 }
 
 // the lane's column of block blk: its number of active layers, 0 for a column that stopped, lies beyond ncol or -- with a label row
@@ -66,8 +57,7 @@ __device__ __forceinline__ int active_layers(const int32_t *n_active, const int3
   const long long col = blk * 64 + lane;
   if (col >= ncol || status[col] != 0) return 0;
   if (labels && labels[col] != group) return 0;
-  const int na = n_active[col];
-  return na < 0 ? 0 : (na > N ? N : na);
+  return layers_within(n_active[col], N);
 }
 
 // ---- layer axis: bin b holds layer b+1 (from the top) or layer N_active-b (from the bottom); bins [b0, b0+nb) of block blk,
@@ -98,7 +88,7 @@ __device__ __forceinline__ void layer_block(const double *__restrict__ lay, long
     for (int u = 0; u < kAhead; ++u) {
       const int k = k0 + u;
       const int r = origin == SAMSIM_PROFILE_FROM_TOP ? k - 1 - b0 : na - k - b0;
-      if (k <= khi && k <= na && r >= 0 && r < nb) sink.put(r, row_value(base + (size_t)(k - 1) * kRow, array, x[u], y[u]));
+      if (k <= khi && k <= na && r >= 0 && r < nb) sink.put(r, requested_value(base + (size_t)(k - 1) * kRow, array, x[u], y[u]));
     }
   }
 }
@@ -112,14 +102,7 @@ __device__ __forceinline__ void depth_block(const double *__restrict__ lay, long
   const bool top = origin == SAMSIM_PROFILE_FROM_TOP;
   const int kmax = wave_max(na);
   const double *base = lay + DEV_LAY_INDEX(0, 0, blk * 64 + lane, N, ncol);   // the lane's element of array 0, layer 1
-  double H = 0.0;
-  if (!top) {   // the ice thickness first: Z_k = Z_{k-1} + thick(k), k ascending
-#pragma unroll 4
-    for (int k = 1; k <= kmax; ++k) {
-      const double t = ld(base + (size_t)(k - 1) * kRow + SAMSIM_A_THICK * 64);
-      H = k <= na ? H + t : H;
-    }
-  }
+  const double H = top ? 0.0 : ice_thickness(base, na, kmax);
   int cur = top ? b0 : b0 + nb - 1;   // the bin the lane's column is filling
   const int step = top ? 1 : -1;
   double Z = 0.0, W = 0.0, L = 0.0;
@@ -153,7 +136,7 @@ __device__ __forceinline__ void depth_block(const double *__restrict__ lay, long
     for (int u = 0; u < kAhead; ++u) {
       const int k = k0 + u;
       if (k <= na) {
-        const double a = row_value(base + (size_t)(k - 1) * kRow, array, x[u], y[u]);
+        const double a = requested_value(base + (size_t)(k - 1) * kRow, array, x[u], y[u]);
         const double Zn = Z + tk[u];
         const double lo = top ? Z : H - Zn, hi = top ? Zn : H - Z;
         while (cur >= b0 && cur < b0 + nb) {

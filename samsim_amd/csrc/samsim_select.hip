@@ -11,11 +11,12 @@
 //
 // Gather: gather_layers_kernel is lay_window<true> of samsim_capi.cpp with a list in place of a window -- one thread per (array,
 // layer, j), j fastest, so the stores into the staging buffer coalesce; the loads are 8 bytes each, 512 B apart within a column
-// block.  The clamp S_abs >= 0 and the quotient S_bu = S_abs / m that samsim_get_state writes to the device before it copies are
-// formed in registers here, under the same conditions: nothing is written to the ensemble, so a column listed twice is read twice
+// block.  The layer value samsim_get_state returns (samsim_column_read.h) is formed in registers here, over the active layers as
+// samsim_get_state adjusts them: nothing is written to the ensemble, so a column listed twice is read twice
 // and races with nothing.  gather_columns_kernel takes the per-column rows the same way.
 #include <hip/hip_runtime.h>
 
+#include "samsim_column_read.h"
 #include "samsim_select.h"
 
 #pragma clang fp contract(off)
@@ -125,17 +126,16 @@ __global__ void __launch_bounds__(256) gather_layers_kernel(const double *__rest
   const int k = (int)(ak % (size_t)N), a = (int)(ak / (size_t)N);
   const size_t c = (size_t)cols[j];
   double v = lay[DEV_LAY_INDEX(a, k, c, N, ncol)];
-  // what samsim_get_state does to the device copy before it reads it: clamp_s_abs and refresh_s_bu of samsim_capi.cpp
-  if (stepped && (a == SAMSIM_A_S_ABS || a == SAMSIM_A_S_BU) && status[c] == 0 && k < n_active[c]) {
-    const bool clamp = (flags[c] & COLF_RESTART) == 0;
-    if (a == SAMSIM_A_S_ABS) {
-      if (clamp && v < 0.0) v = 0.0;
-    } else {
-      const double m = lay[DEV_LAY_INDEX(SAMSIM_A_M, k, c, N, ncol)];
-      if (m != 0.0) {
-        double s = lay[DEV_LAY_INDEX(SAMSIM_A_S_ABS, k, c, N, ncol)];
-        if (clamp && s < 0.0) s = 0.0;
-        v = s / m;
+  // what samsim_get_state does to the device copy before it reads it (clamp_s_abs and refresh_s_bu of samsim_capi.cpp): the layers
+  // below the active ones keep what they hold
+  if (a == SAMSIM_A_S_ABS || a == SAMSIM_A_S_BU) {
+    const column_read::Column q = column_read::column(n_active, status, flags, c, N, stepped != 0);
+    if (q.adjust && k < q.na) {
+      if (a == SAMSIM_A_S_ABS) {
+        v = column_read::s_abs_value(v, q.clamp);
+      } else {
+        const double s = lay[DEV_LAY_INDEX(SAMSIM_A_S_ABS, k, c, N, ncol)], m = lay[DEV_LAY_INDEX(SAMSIM_A_M, k, c, N, ncol)];
+        v = column_read::s_bu_value(s, m, q.adjust, q.clamp, [&] { return v; });
       }
     }
   }

@@ -6,21 +6,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include "samsim_device.h"
+#include "samsim_column_read.h"
+#include "samsim_row_plan.h"
 
-// A walk over the layers serves one group of profile sensors: those whose arrays need at most DEV_SENSOR_GROUP_ROWS distinct rows of
-// the layer block beside thick (S_bu after a step needs two, S_abs and m).  The host deduplicates the rows and forms the groups
-// (sensor_plan, samsim_capi.cpp): a sensor joins the first group in which the union of the rows still fits.  A thermistor string and
-// a salinity core take one walk; in the worst case every sensor has a walk of its own.
-#define DEV_SENSOR_GROUP_ROWS 4
-#define DEV_SENSOR_MAX_GROUPS SAMSIM_MAX_SENSORS
-
-// how the layer value a_k is formed from the loaded rows (as dev_func_mode of samsim_functionals.h)
-enum dev_sensor_mode {
-  DEV_SENSOR_PLAIN = 0,   // the stored value of row ia
-  DEV_SENSOR_S_ABS,       // row ia is S_abs: the health check's clamp where samsim_get_state applies it
-  DEV_SENSOR_S_BU         // row ia is S_abs, row ib is m: the quotient where samsim_get_state forms it, the stored S_bu elsewhere
-};
+// A walk over the layers serves one group of profile sensors: those whose arrays need at most ROW_PLAN_ROWS distinct rows of the
+// layer block beside thick.  The host forms the groups by first-fit (samsim_row_plan.h; sensor_plan, samsim_capi.cpp).  A
+// thermistor string and a salinity core take one walk; in the worst case every sensor has a walk of its own.
 
 // one sensor as the kernel sees it: samsim_sensor_spec, checked by samsim_set_sensors, and its place in the plan
 struct SensorDev {
@@ -28,9 +19,9 @@ struct SensorDev {
   int32_t id;       // SCALAR: enum samsim_scalar
   int32_t origin;   // enum samsim_profile_origin
   int32_t interp;   // enum samsim_sensor_interp
-  int32_t mode;     // enum dev_sensor_mode
+  int32_t mode;     // enum column_read::layer_mode
   int32_t group;    // the walk that serves it (PROFILE), -1 for the other kinds
-  int32_t ia, ib;   // positions among the group's rows; ib only with DEV_SENSOR_S_BU
+  int32_t ia, ib;   // positions among the group's rows; ib only with LAYER_S_BU
   double z, missing;
 };
 
@@ -47,19 +38,16 @@ struct SensorParams {
   long long npos;             // values: positions of this launch
   int32_t N;                  // nlayer
   int32_t ns;                 // sensors
-  int32_t ngroups;
   int32_t stepped;            // the kernel has run: samsim_get_state clamps S_abs and refreshes S_bu in the running columns
   int32_t need_H;             // an ICE_THICKNESS sensor, or a profile sensor that counts from the bottom: a thick-only pre-pass forms H
   int32_t group;              // score: the label a scored column carries, or -1
   uint32_t obs_mask;          // score: bit i set where obs[i] is not a NaN
-  int32_t pad;
-  int32_t gn[DEV_SENSOR_MAX_GROUPS];                          // rows of each group
-  int8_t grow[DEV_SENSOR_MAX_GROUPS][DEV_SENSOR_GROUP_ROWS];  // their arrays (enum samsim_layer_array)
+  RowPlan<SAMSIM_MAX_SENSORS> plan;   // the walks: at most one per profile sensor
   double obs[SAMSIM_MAX_SENSORS], weight[SAMSIM_MAX_SENSORS];
   SensorDev s[SAMSIM_MAX_SENSORS];
 };
 static_assert(SAMSIM_MAX_SENSORS == 32, "one bit per sensor in a 32-bit lane mask");
-static_assert(sizeof(SensorDev) == 48 && sizeof(SensorParams) <= 3072, "the evaluation's parameters travel as a kernel argument");
+static_assert(sizeof(SensorDev) == 48 && sizeof(SensorParams) == 2416, "the evaluation's parameters travel as a kernel argument");
 
 // positions whose values one launch of the list variant leaves in the scratch: [SAMSIM_MAX_SENSORS][DEV_SENSOR_PIECE] doubles, 1 MiB
 #define DEV_SENSOR_PIECE 4096

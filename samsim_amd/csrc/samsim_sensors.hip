@@ -23,8 +23,8 @@
 //
 // Every value is a fixed sequence of IEEE operations on the column's own data: no cross-lane arithmetic beyond the wave maximum of
 // n_active and the votes that skip work, no atomics, plain division, products rounded before they are added (the Makefile's
-// -ffp-contract=off, and the pragma below for a build that drops it).  The layer value is what samsim_get_state would return, formed
-// in registers as samsim_functionals.hip forms it.  Every offset into the rows is 64-bit.
+// -ffp-contract=off, and the pragma below for a build that drops it).  The layer value is what samsim_get_state would return
+// (samsim_column_read.h), formed in registers.  Every offset into the rows is 64-bit.
 #include <hip/hip_runtime.h>
 
 #include "samsim_sensors.h"
@@ -33,29 +33,10 @@
 
 namespace {
 
+using namespace column_read;
+
 constexpr int kAhead = 4;                            // layers whose rows a wave requests before it waits for the first
-constexpr int kRows = DEV_SENSOR_GROUP_ROWS;
-constexpr size_t kRow = DEV_ROWB / sizeof(double);   // doubles from one layer row of a 64-column block to the next
-
-__device__ __forceinline__ int wave_max(int v) {
-  for (int w = 32; w > 0; w >>= 1) { const int o = __shfl_xor(v, w); v = o > v ? o : v; }
-  return v;
-}
-
-__device__ __forceinline__ double ld(const double *p) { return __builtin_nontemporal_load(p); }
-
-// a_k of sensor q in the layer whose loaded rows are x0..x3; row = the lane's element of array 0 of that layer
-__device__ __forceinline__ double value(const SensorDev &q, double x0, double x1, double x2, double x3, const double *row, bool adjust,
-                                        bool clamp) {
-  const double xa = q.ia == 0 ? x0 : (q.ia == 1 ? x1 : (q.ia == 2 ? x2 : x3));
-  if (q.mode == DEV_SENSOR_S_ABS) return (clamp && xa < 0.0) ? 0.0 : xa;
-  if (q.mode == DEV_SENSOR_S_BU) {
-    const double m = q.ib == 0 ? x0 : (q.ib == 1 ? x1 : (q.ib == 2 ? x2 : x3));
-    if (adjust && m != 0.0) return ((clamp && xa < 0.0) ? 0.0 : xa) / m;
-    return ld(row + SAMSIM_A_S_BU * 64);   // a stopped column, or the rare lane with m = 0: the stored value
-  }
-  return xa;
-}
+constexpr int kRows = ROW_PLAN_ROWS;
 
 // between the midpoints of two adjacent layers, (cl, al) of the one with the smaller k and (cu, au) of the other: from the top the
 // smaller k has the smaller coordinate, from the bottom the larger
@@ -76,30 +57,21 @@ __global__ void __launch_bounds__(64) sensors_kernel(const SensorParams p) {
   // a lane beyond the list reads column 0; a lane beyond ncol its own (zero) rows, as the block is allocated whole
   const long long col = LIST ? (in ? p.cols[pos] : 0) : pos;
   const size_t nc = (size_t)p.ncol, c = (size_t)col;
-  int na = 0;
-  bool adjust = false, clamp = false, scored = false;
+  Column cl{};
+  bool scored = false;
   if (in) {
-    const int na_raw = p.n_active[c];
-    const int st = p.status[c];
-    na = na_raw < 0 ? 0 : (na_raw > p.N ? p.N : na_raw);
-    adjust = p.stepped != 0 && st == 0;
-    clamp = adjust && (p.flags[c] & COLF_RESTART) == 0;
+    cl = column(p.n_active, p.status, p.flags, c, p.N, p.stepped != 0);
     if (!LIST) {   // a column that is not scored takes no part in the walk and writes nothing
-      scored = st == 0 && (p.labels == nullptr || p.labels[c] == p.group);
-      if (!scored) na = 0;
+      scored = p.status[c] == 0 && (p.labels == nullptr || p.labels[c] == p.group);
+      if (!scored) cl.na = 0;
     }
   }
+  const int na = cl.na;
+  const bool adjust = cl.adjust, clamp = cl.clamp;
   const int kmax = wave_max(na);
   const double *base = p.lay + DEV_LAY_INDEX(0, 0, c, p.N, nc);   // the lane's element of array 0, layer 1
 
-  double H = 0.0;
-  if (p.need_H) {   // the ice thickness first: Z_k = Z_{k-1} + thick(k), k ascending
-#pragma unroll 4
-    for (int k = 1; k <= kmax; ++k) {
-      const double t = ld(base + (size_t)(k - 1) * kRow + SAMSIM_A_THICK * 64);
-      H = k <= na ? H + t : H;
-    }
-  }
+  const double H = p.need_H ? ice_thickness(base, na, kmax) : 0.0;
 
   // bit i of `found`: sensor i is in the ice; of `pend`: its value waits for the following layer
   uint32_t found = 0, pend = 0;
@@ -113,9 +85,9 @@ __global__ void __launch_bounds__(64) sensors_kernel(const SensorParams p) {
     y[i * 64] = v;
   }
 
-  for (int g = 0; g < p.ngroups; ++g) {
-    const int gn = p.gn[g];
-    const int o0 = p.grow[g][0] * 64, o1 = p.grow[g][1] * 64, o2 = p.grow[g][2] * 64, o3 = p.grow[g][3] * 64;
+  for (int g = 0; g < p.plan.ngroups; ++g) {
+    const int gn = p.plan.gn[g];
+    const int o0 = p.plan.grow[g][0] * 64, o1 = p.plan.grow[g][1] * 64, o2 = p.plan.grow[g][2] * 64, o3 = p.plan.grow[g][3] * 64;
     uint32_t gmask = 0;   // the sensors of this walk (wave-uniform)
     for (int i = 0; i < p.ns; ++i)
       if (p.s[i].group == g) gmask |= 1u << i;
@@ -163,13 +135,13 @@ __global__ void __launch_bounds__(64) sensors_kernel(const SensorParams p) {
           const double *row = row0 + (size_t)u * kRow;
           if (pend & bit) {   // found in layer k - 1, the neighbour is this one
             const double plo = top ? et[u] : eb[u + 1], phi = top ? et[u + 1] : eb[u];
-            const double al = value(q, xx[0][u], xx[1][u], xx[2][u], xx[3][u], row - kRow, adjust, clamp);
-            const double au = value(q, xx[0][u + 1], xx[1][u + 1], xx[2][u + 1], xx[3][u + 1], row, adjust, clamp);
+            const double al = row_value(q.mode, q.ia, q.ib, xx[0][u], xx[1][u], xx[2][u], xx[3][u], row - kRow, adjust, clamp);
+            const double au = row_value(q.mode, q.ia, q.ib, xx[0][u + 1], xx[1][u + 1], xx[2][u + 1], xx[3][u + 1], row, adjust, clamp);
             y[i * 64] = between(top, z, 0.5 * (plo + phi), al, 0.5 * (lo + hi), au);
             pend &= ~bit;
           } else if (lo <= z && z < hi) {   // not found yet, and this is the smallest such k: a sensor is resolved once
             found |= bit;
-            const double ak = value(q, xx[0][u + 1], xx[1][u + 1], xx[2][u + 1], xx[3][u + 1], row, adjust, clamp);
+            const double ak = row_value(q.mode, q.ia, q.ib, xx[0][u + 1], xx[1][u + 1], xx[2][u + 1], xx[3][u + 1], row, adjust, clamp);
             double v = ak;
             if (q.interp == SAMSIM_SENSOR_LINEAR) {
               const double ck = 0.5 * (lo + hi);
@@ -178,7 +150,7 @@ __global__ void __launch_bounds__(64) sensors_kernel(const SensorParams p) {
                 if (k < na) pend |= bit;
               } else if (k > 1) {
                 const double plo = top ? et[u] : eb[u + 1], phi = top ? et[u + 1] : eb[u];
-                const double al = value(q, xx[0][u], xx[1][u], xx[2][u], xx[3][u], row - kRow, adjust, clamp);
+                const double al = row_value(q.mode, q.ia, q.ib, xx[0][u], xx[1][u], xx[2][u], xx[3][u], row - kRow, adjust, clamp);
                 v = between(top, z, 0.5 * (plo + phi), al, ck, ak);
               }
             }

@@ -11,37 +11,28 @@
 // no contraction of d * (x - MEAN) + M2 into a fused multiply-add (the Makefile's -ffp-contract=off, and the pragma below for a
 // build that drops it).  A column that stopped, or a LAYER track whose layer the column does not have, is left alone.
 //
-// The observable is formed from what samsim_get_state would return: S_abs with the health check's clamp S_abs >= 0 applied (the
-// step kernel applies it in the first sweep of the next step, samsim_get_state to what it returns), S_bu as S_abs / m where m != 0.
+// The observable is formed from what samsim_get_state would return (samsim_column_read.h); the sampler only runs behind a step, so
+// it reads its columns as stepped.
 // Every offset into the track rows is 64-bit: ntracks * SAMSIM_NTF * ncol * 8 bytes pass 4 GiB from 6.1 million columns on.
 #include <hip/hip_runtime.h>
 
+#include "samsim_column_read.h"
 #include "samsim_tracks.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+using namespace column_read;
+
 constexpr int kAhead = 8;                            // layers whose rows a wave requests before it waits for the first
-constexpr size_t kRow = DEV_ROWB / sizeof(double);   // doubles from one layer row of a 64-column block to the next
 
-__device__ __forceinline__ int wave_max(int v) {
-  for (int w = 32; w > 0; w >>= 1) { const int o = __shfl_xor(v, w); v = o > v ? o : v; }
-  return v;
-}
-
-// S_abs as samsim_get_state returns it: the health check's clamp, except in a column uploaded since the last step
-__device__ __forceinline__ double clamped(double s_abs, bool clamp) { return (clamp && s_abs < 0.0) ? 0.0 : s_abs; }
-
-// the value of array `a` in the layer row `row` (the lane's element of array 0 of that layer), as samsim_get_state returns it
+// the value of array `a` in the layer row `row` (the lane's element of array 0 of that layer) of a column that runs, with plain loads
 __device__ __forceinline__ double layer_value(const double *row, int a, bool clamp) {
-  if (a == SAMSIM_A_S_BU) {
-    const double s = clamped(row[SAMSIM_A_S_ABS * 64], clamp), m = row[SAMSIM_A_M * 64];
-    if (m != 0.0) return s / m;
-    return row[SAMSIM_A_S_BU * 64];
-  }
+  if (a == SAMSIM_A_S_BU)
+    return s_bu_value(row[SAMSIM_A_S_ABS * 64], row[SAMSIM_A_M * 64], true, clamp, [&] { return row[SAMSIM_A_S_BU * 64]; });
   const double v = row[a * 64];
-  return a == SAMSIM_A_S_ABS ? clamped(v, clamp) : v;
+  return a == SAMSIM_A_S_ABS ? s_abs_value(v, clamp) : v;
 }
 
 __global__ void __launch_bounds__(64) track_sample_kernel(const TrackParams p) {
@@ -51,13 +42,10 @@ __global__ void __launch_bounds__(64) track_sample_kernel(const TrackParams p) {
   const bool live = col < p.ncol && p.status[col] == 0;
   if (!__any(live)) return;
   const size_t nc = (size_t)p.ncol, c = (size_t)col;
-  int na_raw = 0, na = 0;
-  bool clamp = false;
-  if (live) {
-    na_raw = p.n_active[c];
-    na = na_raw < 0 ? 0 : (na_raw > p.N ? p.N : na_raw);
-    clamp = (p.flags[c] & COLF_RESTART) == 0;
-  }
+  Column cl{};
+  if (live) cl = column(p.n_active, p.status, p.flags, c, p.N, true);   // stepped: the sample follows a step launch
+  const int na_raw = cl.na_raw, na = cl.na;
+  const bool clamp = cl.clamp;
   const double *base = p.lay + DEV_LAY_INDEX(0, 0, (size_t)blk * 64 + lane, p.N, nc);   // the lane's element of array 0, layer 1
 
   // ---- the column sums: one walk over the layers, only the rows a track needs
@@ -79,7 +67,7 @@ __global__ void __launch_bounds__(64) track_sample_kernel(const TrackParams p) {
       for (int u = 0; u < kAhead; ++u) {
         if (k0 + u <= na) {   // sequential double additions, k ascending
           Z = Z + tk[u];
-          ssum = ssum + clamped(sa[u], clamp);
+          ssum = ssum + s_abs_value(sa[u], clamp);
           msum = msum + mm[u];
         }
       }

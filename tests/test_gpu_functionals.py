@@ -284,6 +284,16 @@ def test_a_column_does_not_depend_on_its_wave_mates():
     g.set_functionals([SPECS8[i] for i in order])
     assert_rows(rows_of(g, 8), [rows[i] for i in order], "another order")
     g.close()
+    # a list on which the packing matters, on the stepped growth wave: three one-row functionals, then S_bu (S_abs and m: a second
+    # walk), then a fifth array, which joins the first walk by first-fit and would join the second by next-fit
+    g, st, status, _ = stepped()
+    specs = [mk("integral", "T"), mk("max", "psi_l", missing=-1.0), mk("depth_of_max", "ray", "bottom", missing=-1.0),
+             mk("mean", "S_bu", z_hi=0.1, missing=-1.0), mk("min", "H_abs", missing=-1.0)]
+    g.set_functionals(specs)
+    try:
+        assert_rows(rows_of(g, 5), fr.evaluate_all(specs, st, status), "first-fit")
+    finally:
+        g.set_functionals(SPECS_ICE)
 
 
 # ------------------------------------------------------------------------------------------------------------ 6

@@ -254,3 +254,131 @@ int main(void) {
     subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", str(src), "-o", str(exe), "-lm"])
     w15, w4 = (float(v) for v in subprocess.check_output([str(exe)]).decode().split())
     assert w15 <= 3.4e-16 and w4 <= 4.5e-16, (w15, w4)
+
+
+ROW_PLAN_PROGRAM = r'''
+#include <cstdio>
+#include <cstdlib>
+#include "samsim.h"
+#include "samsim_row_plan.h"
+
+struct Item { int a, b; };   // b < 0: one array
+#define CHECK(c) do { if (!(c)) { std::printf("line %d: %s (list %d, item %d)\n", __LINE__, #c, g_list, g_item); std::exit(1); } } while (0)
+static int g_list = -1, g_item = -1;
+
+template <int MAXG> int has(const RowPlan<MAXG> &p, int g, int x) {
+  for (int j = 0; j < p.gn[g]; ++j) if (p.grow[g][j] == x) return 1;
+  return 0;
+}
+template <int MAXG> bool room(const RowPlan<MAXG> &p, int g, Item it) {
+  return p.gn[g] + !has(p, g, it.a) + (it.b >= 0 && !has(p, g, it.b)) <= ROW_PLAN_ROWS;
+}
+
+// plans the list and checks every property of the plan; at[i] = the place of item i
+template <int MAXG> void plan(const Item *it, int n, RowPlan<MAXG> &p, RowPlace *at) {
+  p = RowPlan<MAXG>{};
+  for (int i = 0; i < n; ++i) {
+    g_item = i;
+    const RowPlan<MAXG> before = p;
+    const RowPlace r = at[i] = row_plan_place(p, it[i].a, it[i].b);
+    CHECK(r.group >= 0 && r.group <= before.ngroups && r.group < MAXG);
+    for (int g = 0; g < r.group; ++g) CHECK(!room(before, g, it[i]));   // first-fit: no earlier walk had room for it
+    if (r.group < before.ngroups) CHECK(room(before, r.group, it[i]) && p.ngroups == before.ngroups);
+    else CHECK(p.ngroups == before.ngroups + 1);
+    for (int g = 0; g < before.ngroups; ++g) {   // the rows the earlier items were given stay where they are
+      CHECK(p.gn[g] >= before.gn[g] && (g == r.group || p.gn[g] == before.gn[g]));
+      for (int j = 0; j < before.gn[g]; ++j) CHECK(p.grow[g][j] == before.grow[g][j]);
+    }
+  }
+  g_item = -1;
+  CHECK(p.ngroups >= (n > 0) && p.ngroups <= n);
+  int items[MAXG] = {};
+  for (int i = 0; i < n; ++i) {   // every needed array of an item is among its walk's rows, at ia / ib
+    const RowPlace r = at[i];
+    CHECK(r.group >= 0 && r.group < p.ngroups);
+    ++items[r.group];
+    CHECK(r.ia >= 0 && r.ia < p.gn[r.group] && p.grow[r.group][r.ia] == it[i].a);
+    if (it[i].b >= 0) CHECK(r.ib >= 0 && r.ib < p.gn[r.group] && p.grow[r.group][r.ib] == it[i].b);
+  }
+  for (int g = 0; g < p.ngroups; ++g) {   // no walk is empty, holds a row twice or more than ROW_PLAN_ROWS rows
+    CHECK(items[g] > 0 && p.gn[g] >= 1 && p.gn[g] <= ROW_PLAN_ROWS);
+    for (int j = 0; j < p.gn[g]; ++j) {
+      CHECK(p.grow[g][j] >= 0 && p.grow[g][j] < SAMSIM_NARR);
+      for (int l = 0; l < j; ++l) CHECK(p.grow[g][l] != p.grow[g][j]);
+    }
+  }
+}
+
+static unsigned long long g_seed = 20240917ull;
+static int rnd(int n) {   // a 64-bit LCG (Knuth's MMIX constants), the same lists wherever the program runs
+  g_seed = g_seed * 6364136223846793005ull + 1442695040888963407ull;
+  return (int)((g_seed >> 33) % (unsigned long long)n);
+}
+
+int main() {
+  const int S_BU_ROWS[2] = {SAMSIM_A_S_ABS, SAMSIM_A_M};
+  int walks = 0, two = 0;
+  for (g_list = 0; g_list < 300; ++g_list) {
+    Item it[32];
+    const int n = 1 + rnd(32);
+    const int narr = g_list % 3 == 0 ? SAMSIM_NARR : 3 + rnd(SAMSIM_NARR - 2);   // few arrays: shared rows; many: full walks
+    for (int i = 0; i < n; ++i) {
+      it[i].a = rnd(narr);
+      it[i].b = -1;
+      if (rnd(3) == 0) { do it[i].b = rnd(narr); while (it[i].b == it[i].a); ++two; }
+    }
+    RowPlan<32> p;
+    RowPlace at[32];
+    plan(it, n, p, at);
+    walks += p.ngroups;
+  }
+  CHECK(two > 1000 && walks > 600);   // the lists are not trivial
+  g_list = -1;
+
+  // SPECS_ICE of tests/test_gpu_functionals.py on a handle that has stepped (S_bu reads S_abs and m): five distinct rows, two walks;
+  // the last functional, on S_abs, joins the first walk, where next-fit put it into the second
+  {
+    const Item ice[8] = {{SAMSIM_A_PSI_L, -1}, {SAMSIM_A_PSI_L, -1}, {SAMSIM_A_T, -1}, {S_BU_ROWS[0], S_BU_ROWS[1]},
+                         {SAMSIM_A_PSI_L, -1}, {SAMSIM_A_RAY, -1}, {SAMSIM_A_RAY, -1}, {SAMSIM_A_S_ABS, -1}};
+    const int want[8][3] = {{0, 0, 0}, {0, 0, 0}, {0, 1, 0}, {0, 2, 3}, {0, 0, 0}, {1, 0, 0}, {1, 0, 0}, {0, 2, 0}};
+    RowPlan<8> p;
+    RowPlace at[8];
+    plan(ice, 8, p, at);
+    CHECK(p.ngroups == 2 && p.gn[0] == 4 && p.gn[1] == 1);
+    CHECK(p.grow[0][0] == SAMSIM_A_PSI_L && p.grow[0][1] == SAMSIM_A_T && p.grow[0][2] == SAMSIM_A_S_ABS && p.grow[0][3] == SAMSIM_A_M);
+    CHECK(p.grow[1][0] == SAMSIM_A_RAY);
+    for (g_item = 0; g_item < 8; ++g_item)
+      CHECK(at[g_item].group == want[g_item][0] && at[g_item].ia == want[g_item][1] && at[g_item].ib == want[g_item][2]);
+  }
+  // three one-row items, then S_bu, then a fifth array: the fifth joins the first walk (next-fit: the second, at position 2)
+  {
+    const Item five[5] = {{SAMSIM_A_T, -1}, {SAMSIM_A_PSI_L, -1}, {SAMSIM_A_RAY, -1}, {S_BU_ROWS[0], S_BU_ROWS[1]}, {SAMSIM_A_H_ABS, -1}};
+    RowPlan<8> p;
+    RowPlace at[5];
+    plan(five, 5, p, at);
+    CHECK(p.ngroups == 2 && p.gn[0] == 4 && p.gn[1] == 2);
+    CHECK(at[3].group == 1 && at[3].ia == 0 && at[3].ib == 1);
+    CHECK(at[4].group == 0 && at[4].ia == 3 && p.grow[0][3] == SAMSIM_A_H_ABS);
+  }
+  std::printf("ok %d walks\n", walks);
+  return 0;
+}
+'''
+
+
+def test_row_plan_places_every_item_by_first_fit(tmp_path):
+    """samsim_row_plan.h compiled alone by g++: 300 seeded random lists of up to 32 items that need one or two of the SAMSIM_NARR
+    arrays.  In every plan each needed array of an item is among its walk's rows at ia / ib, no walk holds a row twice, more than
+    four rows or no item, an item is never in a later walk when an earlier one had room (first-fit), and placing an item moves no
+    row of the items before it.  Pinned: the plan of SPECS_ICE on a stepped handle (five distinct rows: two walks) and a list on
+    which first-fit and next-fit differ."""
+    import os
+    import subprocess
+    from tests.helpers import ROOT
+    src = tmp_path / "row_plan.cpp"
+    src.write_text(ROW_PLAN_PROGRAM)
+    exe = tmp_path / "row_plan"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "samsim_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
