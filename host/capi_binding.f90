@@ -128,6 +128,23 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: z, missing
   END TYPE samsim_sensor_spec
 
+  ! samsim_set_weights: the weight row as a slot, enum samsim_weight_kind, how the row is formed and what the call reports of it;
+  ! samsim_get_weighted_stats: the weighted moments of one slot
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_WEIGHT_SLOT = 262144_c_int32_t
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_WEIGHT_DIRECT = 0, SAMSIM_WEIGHT_GAUSS = 1
+  TYPE, BIND(C) :: samsim_weight_spec
+     INTEGER(c_int32_t) :: struct_size, kind, slot, group          ! slot 0-based, -1 = N_active, or samsim_*_slot; group -1 = any
+     REAL(c_double)     :: scale, reserved
+  END TYPE samsim_weight_spec
+  TYPE, BIND(C) :: samsim_weight_info
+     INTEGER(c_int64_t) :: n_in, n_pos
+     REAL(c_double)     :: x_min, sum_w, sum_w2
+  END TYPE samsim_weight_info
+  TYPE, BIND(C) :: samsim_wstat
+     INTEGER(c_int64_t) :: count
+     REAL(c_double)     :: sum_w, sum_w2, mean, var, min, max
+  END TYPE samsim_wstat
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -427,6 +444,37 @@ MODULE mo_samsim_capi
      INTEGER(c_int) FUNCTION samsim_reset_scores(h) BIND(C, name='samsim_reset_scores')
        IMPORT
        TYPE(c_ptr), VALUE :: h
+     END FUNCTION
+     !> form the weight row from a slot (DIRECT w = x, GAUSS w = exp(-(x - x_min) / (2 scale))): SAMSIM_WEIGHT_SLOT is then a slot of
+     !! the ensemble reductions; spec = c_null_ptr (with info = c_null_ptr) removes the row
+     INTEGER(c_int) FUNCTION samsim_set_weights(h, spec, info) BIND(C, name='samsim_set_weights')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(c_ptr), VALUE :: spec                        ! samsim_weight_spec (c_loc of a TARGET), or c_null_ptr
+       TYPE(c_ptr), VALUE :: info                        ! samsim_weight_info (c_loc of a TARGET), or c_null_ptr
+     END FUNCTION
+     !> the window [col0, col0 + ncols) of the weight row
+     INTEGER(c_int) FUNCTION samsim_get_weights(h, col0, ncols, out) BIND(C, name='samsim_get_weights')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: col0, ncols
+       REAL(c_double), INTENT(out) :: out(*)
+     END FUNCTION
+     !> the weighted moments of nslots slots over the running columns with a positive weight -- group >= 0: of those with that label
+     INTEGER(c_int) FUNCTION samsim_get_weighted_stats(h, nslots, slots, group, out) BIND(C, name='samsim_get_weighted_stats')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: nslots, group
+       INTEGER(c_int32_t), INTENT(in) :: slots(*)
+       TYPE(samsim_wstat), INTENT(out) :: out(*)
+     END FUNCTION
+     !> wsum [nvbins + 2]: the sum of the weights per entry of samsim_get_histogram over the same columns
+     INTEGER(c_int) FUNCTION samsim_get_weighted_histogram(h, slot, vb, group, wsum) BIND(C, name='samsim_get_weighted_histogram')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: slot, group
+       TYPE(samsim_hist_bins), INTENT(in) :: vb
+       REAL(c_double), INTENT(out) :: wsum(*)
      END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')

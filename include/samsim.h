@@ -739,6 +739,80 @@ int samsim_get_scores(samsim_handle *h, int64_t col0, int64_t ncols, double *out
 int samsim_set_score_state(samsim_handle *h, int64_t col0, int64_t ncols, const double *in /*[SAMSIM_NSF][ncols]*/);
 int samsim_reset_scores(samsim_handle *h);
 
+/* Posterior statistics: the ensemble weighted by its misfit, on the device.  A perturbed ensemble is scored to get the posterior --
+ * the thickness, an isotherm depth, the melt-onset date GIVEN the buoy's data --, which is every diagnostic above taken with weights
+ * w_c ~ exp(-J_c / 2).  samsim_set_weights forms one row w[ncol] of weights on the device from any slot; the two weighted reductions
+ * read it, and SAMSIM_WEIGHT_SLOT is that row wherever a slot is accepted: the histogram of the weights, the members with w >= 0.01
+ * through samsim_select_columns, the weight as the predictor of samsim_get_profile_regression (which gives the posterior mean of a
+ * depth bin: sum w y / sum w = mean_y + cov / mean_x over the bin's contributing columns).  Nothing here writes to the ensemble:
+ * the calls read slots, status and labels and write the weight row and their own scratch, as samsim_score writes only its rows.  The
+ * entry points below were added without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only.
+ *
+ *   samsim_set_weights.  spec->slot is any slot the reductions accept (a scalar, SAMSIM_STAT_N_ACTIVE, a track row, a functional
+ *     row -- refreshed first, as everywhere --, a score row) but not SAMSIM_WEIGHT_SLOT itself; x is the column's value of it.  A
+ *     column is IN if its status is 0 and, with spec->group >= 0, its label (samsim_set_groups) equals group; group == -1 needs no
+ *     labels.  Every column of the handle is written; a column that is not IN gets w = 0.0.
+ *       SAMSIM_WEIGHT_DIRECT: w = x if x > 0 && x < +inf, else 0.0.  scale must be 0.
+ *       SAMSIM_WEIGHT_GAUSS: x_min = the exact minimum of x over the IN columns whose x is not a NaN, reduced on the device;
+ *         c = 0.5 / scale, one IEEE division on the host; t = (x - x_min) * c, the difference rounded, then the product (no fused
+ *         multiply-add); w = t < 690.0 ? e(-t) : 0.0, where e is the library's fixed sequence of IEEE operations for the exponential
+ *         (within 1 ulp of exp on [-690, 0], e(-0.0) == 1.0 exactly; a host that compiles the same sequence reproduces the row to the
+ *         bit).  A NaN x or a NaN t gives 0.0.  scale = 1 with slot = SAMSIM_SCORE_SLOT(SAMSIM_SF_J_SUM) is the Gaussian likelihood of
+ *         the accumulated misfit relative to the best member; scale > 1 tempers it.  A member with x == x_min has weight exactly 1.0.
+ *         With no IN column that has a non-NaN x, x_min is reported as 0.0 and every weight is 0.0.  x_min of DIRECT is 0.0.
+ *     info (or NULL): n_in = the number of IN columns, n_pos = the number with w > 0, sum_w and sum_w2 the sums of w and w * w over
+ *     them in a fixed order; the effective sample size sum_w * sum_w / sum_w2 is formed on the host.
+ *     Lifetime.  The row is allocated by the first successful call (doubles, 64-bit offsets); a later call replaces its contents;
+ *     samsim_set_weights(h, NULL, NULL) frees it (also when none was set); a call that is refused leaves the previous row in force.
+ *     There is no dirty flag: the row changes only in this call, as the score rows change only in samsim_score.  Stepping,
+ *     samsim_set_state, samsim_set_status and samsim_set_clock leave it alone; it is not part of a checkpoint; samsim_destroy frees it.
+ *   samsim_get_weights.  The window [col0, col0 + ncols) of the row.
+ *   Slots.  While the row exists SAMSIM_WEIGHT_SLOT is accepted wherever a slot is; without it, it is the SAMSIM_ERR_ARG of any bad
+ *     slot.
+ *   samsim_get_weighted_stats.  nslots in 1..SAMSIM_SENS_MAX_SLOTS.  A column COUNTS if its status is 0, its label passes `group` as
+ *     above, and w > 0.  Per slot: count, sum_w = sum of w and sum_w2 = sum of w * w over the counting columns, mean = sum w x / sum w,
+ *     var = sum w (x - mean)^2 / sum w (the reliability-weighted population variance), min and max exact over the counting columns.
+ *     Mean and var are formed from deviations, never as sum w x^2 - ...: in a lane West's update W += w; d = x - mean;
+ *     mean += d * (w / W); M2 += w * d * (x - mean); across lanes and waves the weighted pairwise merge with the cross term
+ *     delta^2 W_a W_b / W, in a fixed order.  count == 0: every double is 0.0.  Columns with identical x give mean == x and
+ *     var == 0.0 exactly.  Two calls on the same state return the same bytes; relabelling columns outside `group` changes nothing.
+ *   samsim_get_weighted_histogram.  Edges and the entry of a value are exactly those of samsim_get_histogram (a NaN lands in entry 0,
+ *     the guessed bin is corrected against the rounded edges); wsum[i] is the sum of w over the counting columns that land in entry
+ *     i, wsum being [nvbins + 2].  One group per call.  The order of summation is fixed: within a wave in ascending column order,
+ *     then the waves' tables in wave order.
+ *   Scratch: at most SAMSIM_WEIGHT_SCRATCH_BYTES of device memory for the three calls whatever ncol is, allocated on first use and
+ *     freed by samsim_destroy.
+ *   Not in scope.  Resampling or any write to the ensemble; weighted profile statistics beyond the regression identity; weighted
+ *     covariances; all groups in one call; weights in checkpoint files.
+ *   Errors, all found before any device work, in this order; a call that is refused writes nothing to the caller's buffers.
+ *     samsim_set_weights: SAMSIM_ERR_ARG for h NULL; with spec NULL: info not NULL is SAMSIM_ERR_ARG, else the row is removed;
+ *     SAMSIM_ERR_ABI for a wrong struct_size; SAMSIM_ERR_ARG for a bad kind; a bad slot or SAMSIM_WEIGHT_SLOT; the group checks of
+ *     samsim_get_covariance; DIRECT with scale != 0; GAUSS with a scale that is not finite or not > 0; reserved != 0.
+ *     SAMSIM_ERR_NOMEM if the row cannot be allocated.  samsim_get_weights: SAMSIM_ERR_ARG for NULL pointers; no row; a window
+ *     outside [0, ncol).  samsim_get_weighted_stats: SAMSIM_ERR_ARG for NULL pointers; nslots outside 1..SAMSIM_SENS_MAX_SLOTS; a bad
+ *     slot; no row; the group checks.  samsim_get_weighted_histogram: the checks of samsim_get_histogram in its order, without
+ *     by_group; no row; the group checks. */
+#define SAMSIM_WEIGHT_SLOT 0x40000
+#define SAMSIM_WEIGHT_SCRATCH_BYTES (4ull << 20)   /* of which 2 MiB are the 1 024 waves' tables of 256 doubles */
+enum samsim_weight_kind { SAMSIM_WEIGHT_DIRECT = 0, SAMSIM_WEIGHT_GAUSS = 1 };
+typedef struct samsim_weight_spec {   /* 32 bytes */
+  int32_t struct_size, kind, slot, group;
+  double  scale, reserved;
+} samsim_weight_spec;
+typedef struct samsim_weight_info {   /* 40 bytes */
+  int64_t n_in, n_pos;
+  double  x_min, sum_w, sum_w2;
+} samsim_weight_info;
+typedef struct samsim_wstat {         /* 56 bytes */
+  int64_t count;
+  double  sum_w, sum_w2, mean, var, min, max;
+} samsim_wstat;
+int samsim_set_weights(samsim_handle *h, const samsim_weight_spec *spec, samsim_weight_info *info /* or NULL */);
+int samsim_get_weights(samsim_handle *h, int64_t col0, int64_t ncols, double *out /*[ncols]*/);
+int samsim_get_weighted_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group, samsim_wstat *out /*[nslots]*/);
+int samsim_get_weighted_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins *vb, int32_t group,
+                                  double *wsum /*[nvbins + 2]*/);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

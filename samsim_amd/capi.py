@@ -236,8 +236,73 @@ def score_slot(field) -> int:
     return 0x30000 + (SF[field] if isinstance(field, str) else int(field))
 
 
+# enum samsim_weight_kind
+WEIGHT_KINDS = {"direct": 0, "gauss": 1}
+
+
+class WeightSpec(C.Structure):
+    """samsim_weight_spec: how the weight row is formed from the slot's value x of the columns that are IN (status 0, label `group` or
+    -1 for any): "direct" w = x where 0 < x < inf, "gauss" w = exp(-(x - x_min) * (0.5 / scale))"""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("slot", C.c_int32), ("group", C.c_int32), ("scale", C.c_double),
+                ("reserved", C.c_double)]
+
+    @staticmethod
+    def make(slot, kind="gauss", scale=1.0, group=None) -> "WeightSpec":
+        """slot a name from SCALARS, "N_active", or an int of track_slot, func_slot or score_slot; kind from WEIGHT_KINDS or its
+        number; scale belongs to "gauss" ("direct" takes none: its field is 0)"""
+        k = WEIGHT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        return WeightSpec(C.sizeof(WeightSpec), k, _slot(slot), -1 if group is None else int(group),
+                          float(scale) if k == WEIGHT_KINDS["gauss"] else 0.0, 0.0)
+
+
+class WeightInfo(C.Structure):
+    """samsim_weight_info"""
+    _fields_ = [("n_in", C.c_int64), ("n_pos", C.c_int64), ("x_min", C.c_double), ("sum_w", C.c_double), ("sum_w2", C.c_double)]
+
+
+WSTAT_DTYPE = np.dtype([("count", np.int64), ("sum_w", np.float64), ("sum_w2", np.float64), ("mean", np.float64), ("var", np.float64),
+                        ("min", np.float64), ("max", np.float64)])
+
+
+def weight_slot() -> int:
+    """SAMSIM_WEIGHT_SLOT: the weight row of set_weights as a slot of ensemble_stats, group_stats, histogram, covariance,
+    profile_regression and select, while the row exists"""
+    return 0x40000
+
+
+def weighted_quantile_bracket(wsum, v0, dv, q):
+    """(lo, hi) with the weighted q-quantile of the data in [lo, hi), from the sums of Solver.weighted_histogram (nvbins + 2
+    entries): the quantile is the smallest value whose cumulative weight reaches q times the total; i = the first entry of positive
+    weight whose cumulative sum reaches that, lo = E_{i-1} and hi = E_i, with -inf and +inf for the two outer entries"""
+    wsum = np.asarray(wsum, dtype=np.float64)
+    if wsum.ndim != 1 or wsum.size < 3:
+        raise ValueError("one row of nvbins + 2 sums is needed")
+    if not (wsum >= 0.0).all():
+        raise ValueError("a sum of weights is negative or a NaN")
+    cum = np.cumsum(wsum)
+    if not cum[-1] > 0.0:
+        raise ValueError("an empty row has no quantiles")
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("q outside [0, 1]")
+    i = min(int(np.searchsorted(cum, q * cum[-1], side="left")), wsum.size - 1)
+    while wsum[i] == 0.0:       # q == 0, or a target met exactly at an entry's end: the next entry that holds weight
+        i += 1
+    e = hist_edges(wsum.size - 2, v0, dv)
+    return (-np.inf if i == 0 else float(e[i - 1])), (np.inf if i == wsum.size - 1 else float(e[i]))
+
+
+def weighted_profile_mean(pair_stats) -> np.ndarray:
+    """the weighted mean of the bin value y per bin, sum w y / sum w over the bin's contributing columns, from an array of
+    PAIR_STAT_DTYPE that Solver.profile_regression returned with predictor=weight_slot(): mean_y + cov / mean_x (cov = mean(w y) -
+    mean_w mean_y and mean_x = mean_w over the same columns); 0.0 where mean_x == 0 (no weight in the bin)"""
+    q = np.asarray(pair_stats)
+    mx = q["mean_x"]
+    ok = mx != 0.0
+    return np.where(ok, q["mean_y"] + q["cov"] / np.where(ok, mx, 1.0), 0.0)
+
+
 def _slot(name) -> int:
-    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot, func_slot or score_slot gives it"""
+    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot, func_slot, score_slot or weight_slot gives it"""
     if isinstance(name, (int, np.integer)):
         return int(name)
     return -1 if name == "N_active" else S[name]
@@ -497,6 +562,14 @@ class Solver:
                       "score": [vp, C.c_void_p, C.c_void_p, C.c_int32], "get_scores": [vp, i64, i64, C.c_void_p],
                       "set_score_state": [vp, i64, i64, C.c_void_p], "reset_scores": [vp]}
         for n, a in sensor_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the weight row and the weighted reductions
+        weight_sig = {"set_weights": [vp, C.POINTER(WeightSpec), C.POINTER(WeightInfo)], "get_weights": [vp, i64, i64, C.c_void_p],
+                      "get_weighted_stats": [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_void_p],
+                      "get_weighted_histogram": [vp, C.c_int32, C.POINTER(HistBins), C.c_int32, C.c_void_p]}
+        for n, a in weight_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -935,6 +1008,65 @@ class Solver:
     def reset_scores(self):
         """every score row back to 0.0 (samsim_reset_scores)"""
         self._chk(self._f("reset_scores")(self._h), "reset_scores")
+
+    # -- the weight row and the weighted (posterior) reductions
+    def set_weights_raw(self, spec, info=None):
+        """samsim_set_weights with the arguments as given (no checks on this side): spec a WeightSpec or None, info a WeightInfo or
+        None"""
+        self._chk(self._f("set_weights")(self._h, None if spec is None else C.byref(spec), None if info is None else C.byref(info)),
+                  "set_weights")
+
+    def set_weights(self, slot, kind="gauss", scale=1.0, group=None):
+        """form the weight row on the device from the slot's values of the running columns -- with group: of those with that label
+        of set_groups; every other column gets 0 -- (samsim_set_weights): "gauss" w = exp(-(x - x_min) / (2 scale)), with
+        slot=score_slot("J_SUM") the likelihood of the accumulated misfit relative to the best member; "direct" w = x where
+        0 < x < inf.  weight_slot() is then the row wherever a slot is accepted.  Returns {"n_in", "n_pos", "x_min", "sum_w",
+        "sum_w2", "ess"}, ess = sum_w^2 / sum_w2 the effective sample size (0.0 without a positive weight)"""
+        info = WeightInfo()
+        self.set_weights_raw(WeightSpec.make(slot, kind, scale, group), info)
+        ess = info.sum_w * info.sum_w / info.sum_w2 if info.sum_w2 > 0.0 else 0.0
+        return {"n_in": int(info.n_in), "n_pos": int(info.n_pos), "x_min": info.x_min, "sum_w": info.sum_w, "sum_w2": info.sum_w2,
+                "ess": ess}
+
+    def clear_weights(self):
+        """remove the weight row (samsim_set_weights with NULL), also when none was set"""
+        self.set_weights_raw(None)
+
+    def weights(self, col0: int = 0, ncols: int | None = None) -> np.ndarray:
+        """float64 [ncols]: the weights of the columns [col0, col0 + ncols) (samsim_get_weights)"""
+        n = self.ncol - col0 if ncols is None else ncols
+        buf = np.zeros(max(0, n))
+        self._chk(self._f("get_weights")(self._h, col0, n, buf.ctypes.data), "get_weights")
+        return buf
+
+    def weighted_stats_raw(self, slots, group=-1) -> np.ndarray:
+        """samsim_get_weighted_stats with the arguments as given (no checks on this side): WSTAT_DTYPE [nslots]"""
+        slots = [int(x) for x in slots]
+        n = len(slots)
+        arr = (C.c_int32 * max(1, n))(*slots)
+        out = np.zeros(max(1, min(n, SENS_MAX_SLOTS)), dtype=WSTAT_DTYPE)
+        self._chk(self._f("get_weighted_stats")(self._h, n, arr, int(group), out.ctypes.data), "get_weighted_stats")
+        return out[:max(0, min(n, SENS_MAX_SLOTS))]
+
+    def weighted_stats(self, names, group=None):
+        """{name: WSTAT_DTYPE record} of the slots `names` (from SCALARS, "N_active", or ints of track_slot, func_slot, score_slot)
+        over the running columns with a positive weight -- with group: of those with that label -- (samsim_get_weighted_stats):
+        count, sum_w, sum_w2, the weighted mean, the weighted population variance sum w (x - mean)^2 / sum w, min and max"""
+        names = list(names)
+        out = self.weighted_stats_raw([_slot(n) for n in names], -1 if group is None else int(group))
+        return {n: out[i] for i, n in enumerate(names)}
+
+    def weighted_histogram_raw(self, slot, vb: HistBins, group=-1) -> np.ndarray:
+        """samsim_get_weighted_histogram with the arguments as given (no checks on this side): float64 [nvbins+2]"""
+        buf = np.zeros(max(0, min(vb.nvbins, HIST_MAX_VBINS)) + 2)
+        self._chk(self._f("get_weighted_histogram")(self._h, int(slot), C.byref(vb), int(group), buf.ctypes.data), "get_weighted_histogram")
+        return buf
+
+    def weighted_histogram(self, name, nvbins, v0, dv, group=None) -> np.ndarray:
+        """the sum of the weights per entry of histogram() over the running columns with a positive weight -- with group: of those
+        with that label -- (samsim_get_weighted_histogram): float64 [nvbins+2]; capi.weighted_quantile_bracket reads quantiles off
+        it"""
+        return self.weighted_histogram_raw(_slot(name), hist_bins(nvbins, v0, dv), -1 if group is None else int(group))
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

@@ -22,6 +22,7 @@
 #include "samsim_sensors.h"
 #include "samsim_sens.h"
 #include "samsim_tracks.h"
+#include "samsim_weights.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
 // samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS) over every column
@@ -89,6 +90,8 @@ struct samsim_handle {
   double *score_rows = nullptr; // [SAMSIM_NSF][ncol] rows of the per-column misfit (samsim_set_sensors), updated by samsim_score
   int32_t nsensors = 0;        // 0: no sensors
   samsim_sensor_spec sensor[SAMSIM_MAX_SENSORS]{};
+  double *weight_row = nullptr; // [ncol] weights of the columns (samsim_set_weights), changed by that call alone
+  void *d_weight = nullptr;    // samsim_set_weights and the weighted reductions: the waves' tables and partials, then the results (kWeightScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -245,6 +248,11 @@ constexpr size_t kSelectScratch = DEV_SEL_BYTES;
 static_assert(kSelectScratch <= SAMSIM_SELECT_SCRATCH_BYTES && SAMSIM_SELECT_SCRATCH_BYTES <= (16ull << 20), "select scratch bound of samsim.h");
 static_assert(sizeof(samsim_select_term) == 24 && sizeof(samsim_selection) == 24 + 24 * SAMSIM_SELECT_MAX_TERMS, "samsim_selection of samsim.h");
 static_assert((size_t)SAMSIM_SELECT_MAX_OUT * DEV_SEL_COLUMN_BYTES <= kStageBytes, "the per-column rows of the largest request are one piece");
+
+// device scratch of the weight row and the weighted reductions: the waves' histogram tables, their partials, then the results
+constexpr size_t kWeightScratch = DEV_WEIGHT_BYTES;
+static_assert(kWeightScratch <= SAMSIM_WEIGHT_SCRATCH_BYTES && SAMSIM_WEIGHT_SCRATCH_BYTES <= (16ull << 20), "weight scratch bound of samsim.h");
+static_assert(sizeof(samsim_weight_spec) == 32 && sizeof(samsim_weight_info) == 40 && sizeof(samsim_wstat) == 56, "the weight structs of samsim.h");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -428,13 +436,15 @@ int launch(samsim_handle *h, long long nsteps) {
 }
 
 // a slot of the statistics: an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE, SAMSIM_TRACK_SLOT(track, field) of the tracks in force, or
-// SAMSIM_FUNC_SLOT(i) of the functionals in force, or SAMSIM_SCORE_SLOT(field) while sensors are set
+// SAMSIM_FUNC_SLOT(i) of the functionals in force, or SAMSIM_SCORE_SLOT(field) while sensors are set, or SAMSIM_WEIGHT_SLOT while the
+// weight row exists
 bool func_slot(int32_t slot) { return slot >= SAMSIM_FUNC_SLOT(0) && slot < SAMSIM_FUNC_SLOT(SAMSIM_MAX_FUNCTIONALS); }
 bool score_slot(int32_t slot) { return slot >= SAMSIM_SCORE_SLOT(0) && slot < SAMSIM_SCORE_SLOT(SAMSIM_NSF); }
 bool good_slot(const samsim_handle *h, int32_t slot) {
   if (slot == SAMSIM_STAT_N_ACTIVE || (slot >= 0 && slot < SAMSIM_NSCAL)) return true;
   if (func_slot(slot)) return h->func_rows && slot - SAMSIM_FUNC_SLOT(0) < h->nfunc;
   if (score_slot(slot)) return h->score_rows != nullptr;
+  if (slot == SAMSIM_WEIGHT_SLOT) return h->weight_row != nullptr;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks && o >= 0 && o / 32 < h->ntracks && o % 32 < SAMSIM_NTF;
 }
@@ -444,6 +454,7 @@ const double *slot_row(const samsim_handle *h, int32_t slot) {
   if (slot < SAMSIM_NSCAL) return h->scal + (size_t)slot * (size_t)h->ncol;
   if (func_slot(slot)) return h->func_rows + (size_t)(slot - SAMSIM_FUNC_SLOT(0)) * (size_t)h->ncol;
   if (score_slot(slot)) return h->score_rows + (size_t)(slot - SAMSIM_SCORE_SLOT(0)) * (size_t)h->ncol;
+  if (slot == SAMSIM_WEIGHT_SLOT) return h->weight_row;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks + ((size_t)(o / 32) * SAMSIM_NTF + (size_t)(o % 32)) * (size_t)h->ncol;
 }
@@ -622,6 +633,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens); (void)hipFree(h->tracks);
   (void)hipFree(h->func_rows);
   (void)hipFree(h->score_rows);
+  (void)hipFree(h->weight_row); (void)hipFree(h->d_weight);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -1698,6 +1710,113 @@ int samsim_reset_scores(samsim_handle *h) {
   int rc = use(h);
   if (rc) return rc;
   HIPCHK(zero_scores(h, h->score_rows));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_set_weights(samsim_handle *h, const samsim_weight_spec *spec, samsim_weight_info *info) {
+  // every check first, in the order samsim.h gives: a call that is refused leaves the previous row in force
+  if (!h) return SAMSIM_ERR_ARG;
+  if (!spec) {
+    if (info) return SAMSIM_ERR_ARG;
+    int rc = use(h);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->weight_row);
+    h->weight_row = nullptr;
+    return SAMSIM_OK;
+  }
+  if (spec->struct_size != (int32_t)sizeof(samsim_weight_spec)) return SAMSIM_ERR_ABI;
+  if (spec->kind != SAMSIM_WEIGHT_DIRECT && spec->kind != SAMSIM_WEIGHT_GAUSS) return SAMSIM_ERR_ARG;
+  if (spec->slot == SAMSIM_WEIGHT_SLOT || !good_slot(h, spec->slot)) return SAMSIM_ERR_ARG;
+  if (!good_group(h, spec->group)) return SAMSIM_ERR_ARG;
+  if (spec->kind == SAMSIM_WEIGHT_DIRECT && spec->scale != 0.0) return SAMSIM_ERR_ARG;
+  if (spec->kind == SAMSIM_WEIGHT_GAUSS && !(std::isfinite(spec->scale) && spec->scale > 0.0)) return SAMSIM_ERR_ARG;
+  if (spec->reserved != 0.0) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  // the row of the first call, kept and rewritten by the later ones (the source is never the row itself)
+  double *row = h->weight_row;
+  if (!row && dalloc(&row, (size_t)h->ncol) != hipSuccess) {
+    (void)hipGetLastError();
+    return SAMSIM_ERR_NOMEM;
+  }
+  const bool fresh = !h->weight_row;
+  rc = func_refresh_for(h, 1, &spec->slot);
+  if (!rc && !h->d_weight && !hip_ok(hipMalloc(&h->d_weight, kWeightScratch), "hipMalloc weight scratch")) rc = SAMSIM_ERR_HIP;
+  if (rc) {
+    if (fresh) (void)hipFree(row);
+    return rc;
+  }
+  h->weight_row = row;
+  WeightPartial *d_part = (WeightPartial *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
+  WeightPartial *d_out = (WeightPartial *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
+  const double c = spec->kind == SAMSIM_WEIGHT_GAUSS ? 0.5 / spec->scale : 0.0;
+  HIPCHK(samsim_launch_set_weights(slot_row(h, spec->slot), h->n_active, h->status, spec->group >= 0 ? h->groups : nullptr, spec->group,
+                                   h->ncol, spec->kind, c, row, d_part, d_out, h->stream));
+  WeightPartial res;
+  HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(WeightPartial), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (info) *info = samsim_weight_info{res.n_in, res.n_pos, res.x_min, res.sum_w, res.sum_w2};
+  return SAMSIM_OK;
+}
+
+int samsim_get_weights(samsim_handle *h, int64_t col0, int64_t ncols, double *out) {
+  if (!h || !out) return SAMSIM_ERR_ARG;
+  if (!h->weight_row) return SAMSIM_ERR_ARG;
+  int rc = check_window(h, col0, ncols);
+  if (rc) return rc;
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  HIPCHK(hipMemcpy(out, h->weight_row + (size_t)col0, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+int samsim_get_weighted_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group, samsim_wstat *out) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !slots || !out) return SAMSIM_ERR_ARG;
+  if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < nslots; ++i)
+    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
+  if (!h->weight_row) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  rc = func_refresh_for(h, nslots, slots);
+  if (rc) return rc;
+  if (!h->d_weight) HIPCHK(hipMalloc(&h->d_weight, kWeightScratch));
+  WStatPartial *d_part = (WStatPartial *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
+  samsim_wstat *d_out = (samsim_wstat *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
+  SensRows rows{};
+  for (int i = 0; i < nslots; ++i) rows.row[i] = slot_row(h, slots[i]);
+  HIPCHK(samsim_launch_weighted_stats(rows, nslots, h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol,
+                                      d_part, d_out, h->stream));
+  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_wstat) * (size_t)nslots, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_get_weighted_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins *vb, int32_t group, double *wsum) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !vb || !wsum) return SAMSIM_ERR_ARG;
+  HistEdges e;
+  int rc = check_hist_bins(vb, &e);
+  if (rc) return rc;
+  if (!good_slot(h, slot)) return SAMSIM_ERR_ARG;
+  if (!h->weight_row) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  rc = func_refresh_for(h, 1, &slot);
+  if (rc) return rc;
+  if (!h->d_weight) HIPCHK(hipMalloc(&h->d_weight, kWeightScratch));
+  double *d_tables = (double *)((char *)h->d_weight + DEV_WEIGHT_TABLES_AT);
+  double *d_out = (double *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
+  HIPCHK(samsim_launch_weighted_hist(slot_row(h, slot), h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group,
+                                     h->ncol, e, d_tables, d_out, h->stream));
+  HIPCHK(hipMemcpyAsync(wsum, d_out, sizeof(double) * (size_t)(e.nvbins + 2), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }

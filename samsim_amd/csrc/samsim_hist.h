@@ -38,6 +38,18 @@ static inline size_t dev_hist_profile_lds(int nvbins) {
 // the edges of a request: E_j = v0 + j*dv (product rounded, then the sum); rdv = 1/dv only serves the device's first guess
 struct HistEdges { double v0, dv, rdv; int nvbins; };
 
+// The entry of a value, the one rule the histograms of samsim_hist.hip and the weighted one of samsim_weights.hip count by: the
+// number of edges E_j = v0 + j*dv, j = 0..nvbins, with E_j <= v.  The quotient only guesses j; the guess is then moved until E_j <= v < E_{j+1} holds for the rounded edges themselves (the host has checked that they increase strictly).
+// A NaN compares false and lands in entry 0.
+__device__ __forceinline__ int hist_entry(double v, const HistEdges &e) {
+  if (!(v >= e.v0)) return 0;   // below E_0 = v0 + 0*dv = v0, or NaN
+  const double t = (v - e.v0) * e.rdv;
+  int j = t >= (double)e.nvbins ? e.nvbins : (t > 0.0 ? (int)t : 0);   // the largest j with E_j <= v, if the guess is right
+  while (j < e.nvbins && e.v0 + (double)(j + 1) * e.dv <= v) ++j;
+  while (j > 0 && e.v0 + (double)j * e.dv > v) --j;
+  return j + 1;
+}
+
 // samsim_hist.hip.  counts: the 64-bit result table in device memory, zero before the first pass of a request.
 // Scalars: the histogram of one row (row, or n_active where row is null) per group -- labels null: one group of every column with
 // status 0 --, counts[ngroups][W].

@@ -17,18 +17,6 @@ namespace {
 
 using namespace profile_walk;
 
-// The entry of a value: the number of edges E_j = v0 + j*dv, j = 0..nvbins, with E_j <= v.  The quotient only guesses j; the guess
-// is then moved until E_j <= v < E_{j+1} holds for the rounded edges themselves (the host has checked that they increase strictly).
-// A NaN compares false and lands in entry 0.
-__device__ __forceinline__ int hist_entry(double v, const HistEdges &e) {
-  if (!(v >= e.v0)) return 0;   // below E_0 = v0 + 0*dv = v0, or NaN
-  const double t = (v - e.v0) * e.rdv;
-  int j = t >= (double)e.nvbins ? e.nvbins : (t > 0.0 ? (int)t : 0);   // the largest j with E_j <= v, if the guess is right
-  while (j < e.nvbins && e.v0 + (double)(j + 1) * e.dv <= v) ++j;
-  while (j > 0 && e.v0 + (double)j * e.dv > v) --j;
-  return j + 1;
-}
-
 // what a wave counted, added to the 64-bit result
 __device__ __forceinline__ void flush_table(const uint32_t *table, int n, int lane, unsigned long long *out) {
   for (int i = lane; i < n; i += 64) {

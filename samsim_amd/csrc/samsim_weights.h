@@ -1,0 +1,54 @@
+// samsim_weights.h -- what samsim_weights.hip and the C-ABI host code share about the weight row and the weighted reductions
+// (samsim_set_weights, samsim_get_weighted_stats, samsim_get_weighted_histogram, include/samsim.h).  The step kernel does not
+// include this header.
+#ifndef SAMSIM_WEIGHTS_H
+#define SAMSIM_WEIGHTS_H
+
+#include <hip/hip_runtime.h>
+
+#include "samsim_hist.h"
+#include "samsim_sens.h"
+
+// Every kernel runs a fixed grid of at most DEV_WEIGHT_GRID one-wave workgroups (a wave per 64-column block at a time), fixed by
+// ncol alone; every wave leaves one partial, merged in wave order.
+#define DEV_WEIGHT_GRID 1024
+#define DEV_WEIGHT_ENTRIES (SAMSIM_HIST_MAX_VBINS + 2)   // a wave's table of the weighted histogram
+
+// what a wave knows of the columns it saw.  samsim_set_weights: the minimum of x over the IN columns with a non-NaN x and how many
+// there were (n_pos), then n_in, n_pos, sum_w, sum_w2 of the row it wrote
+struct WeightPartial { double x_min, sum_w, sum_w2; long long n_in, n_pos; };
+// samsim_get_weighted_stats: n columns of total weight W (and sum of squared weights W2) with weighted mean `mean` and weighted sum
+// of squared deviations m2
+struct WStatPartial { double W, W2, mean, m2, mn, mx; long long n; };
+
+// device scratch of the three calls: the waves' histogram tables, the waves' partials (every pass reuses them), then the results
+#define DEV_WEIGHT_TABLES_AT 0
+#define DEV_WEIGHT_TABLES_BYTES (sizeof(double) * DEV_WEIGHT_GRID * DEV_WEIGHT_ENTRIES)
+#define DEV_WEIGHT_PART_AT (DEV_WEIGHT_TABLES_AT + DEV_WEIGHT_TABLES_BYTES)
+#define DEV_WEIGHT_PART_BYTES (sizeof(WStatPartial) * DEV_WEIGHT_GRID * SAMSIM_SENS_MAX_SLOTS)   // [wave][slot]
+static_assert(sizeof(WeightPartial) <= sizeof(WStatPartial), "the partials of samsim_set_weights fit where the statistics' do");
+#define DEV_WEIGHT_RESULT_AT (DEV_WEIGHT_PART_AT + DEV_WEIGHT_PART_BYTES)
+#define DEV_WEIGHT_RESULT_BYTES (sizeof(double) * DEV_WEIGHT_ENTRIES)
+static_assert(sizeof(samsim_wstat) * SAMSIM_SENS_MAX_SLOTS <= DEV_WEIGHT_RESULT_BYTES && sizeof(WeightPartial) <= DEV_WEIGHT_RESULT_BYTES,
+              "the results of the other two calls fit where a histogram row does");
+#define DEV_WEIGHT_BYTES (DEV_WEIGHT_RESULT_AT + DEV_WEIGHT_RESULT_BYTES)
+static_assert(DEV_WEIGHT_BYTES <= SAMSIM_WEIGHT_SCRATCH_BYTES, "weight scratch bound of samsim.h");
+
+// samsim_weights.hip.  x: the [ncol] row of the source slot, or null for n_active.  labels: null (every column with status 0 is
+// IN), or the label row of samsim_set_groups, of which only the columns with label `group` are.  part and out lie in the handle's
+// scratch; the calls only enqueue.
+// The weight row w[ncol] of `kind` (enum samsim_weight_kind) with c = 0.5 / scale; out: x_min, sum_w, sum_w2, n_in, n_pos.
+extern "C" hipError_t samsim_launch_set_weights(const double *x, const int32_t *n_active, const int32_t *status, const int32_t *labels,
+                                                int group, long long ncol, int kind, double c, double *w, WeightPartial *part,
+                                                WeightPartial *out, hipStream_t stream);
+// the weighted moments of the nslots rows (SensRows of samsim_sens.h: a null row is n_active) over the columns that are IN and have
+// w > 0, in one walk, to out[0 .. nslots)
+extern "C" hipError_t samsim_launch_weighted_stats(SensRows rows, int nslots, const double *w, const int32_t *n_active,
+                                                   const int32_t *status, const int32_t *labels, int group, long long ncol,
+                                                   WStatPartial *part, samsim_wstat *out, hipStream_t stream);
+// the sum of w per entry of the histogram of one row over the same columns: tables [grid][DEV_WEIGHT_ENTRIES], out [nvbins + 2]
+extern "C" hipError_t samsim_launch_weighted_hist(const double *x, const double *w, const int32_t *n_active, const int32_t *status,
+                                                  const int32_t *labels, int group, long long ncol, HistEdges e, double *tables, double *out,
+                                                  hipStream_t stream);
+
+#endif
