@@ -476,6 +476,28 @@ MODULE mo_samsim_capi
        TYPE(samsim_hist_bins), INTENT(in) :: vb
        REAL(c_double), INTENT(out) :: wsum(*)
      END FUNCTION
+     !> per bin of a profile request the weighted moments of the bin value over the running columns with a positive weight that
+     !! contribute to the bin -- group >= 0: of those with that label, -1 = any --; out(nbins, narrays), bin fastest
+     INTEGER(c_int) FUNCTION samsim_get_weighted_profile_stats(h, rq, group, out) BIND(C, name='samsim_get_weighted_profile_stats')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(samsim_profile_request), INTENT(in) :: rq
+       INTEGER(c_int32_t), VALUE :: group
+       TYPE(samsim_wstat), INTENT(out) :: out(*)
+     END FUNCTION
+     !> the weighted means and the weighted population covariances of nslots slots over the same columns; cov(nslots, nslots) is
+     !! symmetric, its diagonal the var of samsim_get_weighted_stats
+     INTEGER(c_int) FUNCTION samsim_get_weighted_covariance(h, nslots, slots, group, count, sum_w, sum_w2, mean, cov) &
+          BIND(C, name='samsim_get_weighted_covariance')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: nslots
+       INTEGER(c_int32_t), INTENT(in) :: slots(*)
+       INTEGER(c_int32_t), VALUE :: group
+       INTEGER(c_int64_t), INTENT(out) :: count
+       REAL(c_double), INTENT(out) :: sum_w, sum_w2
+       REAL(c_double), INTENT(out) :: mean(*), cov(*)
+     END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')
        IMPORT

@@ -782,8 +782,8 @@ int samsim_reset_scores(samsim_handle *h);
  *     then the waves' tables in wave order.
  *   Scratch: at most SAMSIM_WEIGHT_SCRATCH_BYTES of device memory for the three calls whatever ncol is, allocated on first use and
  *     freed by samsim_destroy.
- *   Not in scope.  Resampling or any write to the ensemble; weighted profile statistics beyond the regression identity; weighted
- *     covariances; all groups in one call; weights in checkpoint files.
+ *   Not in scope.  Resampling or any write to the ensemble; all groups in one call; weights in checkpoint files.  (Weighted profile
+ *     statistics and weighted covariances are the two entry points of the next block.)
  *   Errors, all found before any device work, in this order; a call that is refused writes nothing to the caller's buffers.
  *     samsim_set_weights: SAMSIM_ERR_ARG for h NULL; with spec NULL: info not NULL is SAMSIM_ERR_ARG, else the row is removed;
  *     SAMSIM_ERR_ABI for a wrong struct_size; SAMSIM_ERR_ARG for a bad kind; a bad slot or SAMSIM_WEIGHT_SLOT; the group checks of
@@ -812,6 +812,63 @@ int samsim_get_weights(samsim_handle *h, int64_t col0, int64_t ncols, double *ou
 int samsim_get_weighted_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group, samsim_wstat *out /*[nslots]*/);
 int samsim_get_weighted_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins *vb, int32_t group,
                                   double *wsum /*[nvbins + 2]*/);
+
+/* Posterior profiles and posterior sensitivities: the weight row applied to the layer profiles and to the joint moments of the
+ * column scalars.  samsim_get_weighted_profile_stats is samsim_get_profile_stats with weights -- per depth bin the posterior mean of
+ * T(z), S_bu(z) or psi_l(z) with its variance, its extremes and the sums from which the effective sample size of the bin follows --,
+ * samsim_get_weighted_covariance is samsim_get_covariance with weights: how the thickness co-varies with dT2m GIVEN the buoy's data.
+ * Both are read-only reductions: they read slots, status, labels, the layer block and the weight row and write only their own
+ * scratch.  The entry points below were added without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only.
+ *
+ *   Columns (both).  A column COUNTS as in samsim_get_weighted_stats: its status is 0, its label passes `group` (-1: every label, no
+ *     labels needed; >= 0: only that label of samsim_set_groups), and its weight w > 0.  One group per call.
+ *   samsim_get_weighted_profile_stats.  rq is a request of samsim_get_profile_stats with any narrays; out[narrays][nbins].  The bins,
+ *     the layer value a_k and the per-column bin value v are exactly those of that function, and a counting column contributes to a
+ *     bin under exactly that function's condition (BY_LAYER: the layer exists; BY_DEPTH: L_b > 0); a column that does not count
+ *     behaves like a stopped one.  Per (array, bin), over the counting columns that contribute: count, sum_w = sum of w,
+ *     sum_w2 = sum of w * w, mean = sum w v / sum w, var = sum w (v - mean)^2 / sum w, min and max exact.  The contributing columns
+ *     differ from bin to bin, so sum_w and sum_w2 are per-bin results; the effective sample size of a bin, sum_w^2 / sum_w2, is
+ *     formed on the host.  With count == 0 every double is 0.0.  A request is served in passes of one array and at most 64 bins, as
+ *     samsim_get_profile_stats is.
+ *     Arithmetic.  The walk, the grid, the chunks and the wave order are those of samsim_get_profile_stats.  A wave folds the bin's
+ *     values of one 64-column block in column order: mean_b = ref + (sum w_i (v_i - ref)) / (sum w_i) around the first counting value
+ *     ref, then M2_b = sum w_i * (d_i * d_i), d_i = v_i - mean_b, in a second walk; blocks and then waves are merged in a fixed
+ *     order by Chan's update with the total weight W in the place of the count: fb = W_b / W, mean += delta * fb,
+ *     M2 += M2_b + delta * delta * (W_a * fb); var = M2 / W.  No fused multiply-add, no atomics, a grid fixed by ncol alone.
+ *     Properties.  Two calls on the same state return the same bytes; relabelling or re-weighting columns outside `group` changes
+ *     nothing.  Columns that hold identical v in a bin give mean == v == min == max and var == 0.0 exactly, whatever the weights.
+ *     When every counting column has w == 1.0, count, mean, min and max are the bytes of samsim_get_profile_stats for the same
+ *     request (samsim_get_group_profile_stats with a group), sqrt(var) is its std bytes, and sum_w == sum_w2 == (double)count:
+ *     every product with w is then exact and every W an exactly represented integer.
+ *   samsim_get_weighted_covariance.  nslots in 1..SAMSIM_SENS_MAX_SLOTS; the slots are those samsim_get_weighted_stats accepts
+ *     (functional rows are refreshed first; SAMSIM_WEIGHT_SLOT itself is allowed; a slot may appear twice).  count, sum_w and sum_w2
+ *     over the counting columns; mean[i] = sum w x_i / sum w; cov[i][j] = sum w (x_i - mean_i)(x_j - mean_j) / sum w, the diagonal
+ *     the weighted variance.  One triangle is computed and mirrored: cov[i][j] and cov[j][i] are the same bytes.  With count == 0
+ *     every output is 0.0.
+ *     Arithmetic.  One walk serves all slots.  In a lane West's update of samsim_get_weighted_stats for the means and
+ *     C_ij += w * d_i * (x_j - mean_j), d_i = x_i - mean_i before the update and mean_j after it; across lanes and waves the weighted
+ *     pairwise merge with the cross term delta_i delta_j W_a W_b / W, in the order of samsim_get_weighted_stats.  No atomics.
+ *     Properties.  Two calls return the same bytes; relabelling columns outside `group` changes nothing.  A slot listed twice gives
+ *     cov[i][j] == cov[i][i] == cov[j][j] bitwise.  Identical columns give covariances of exactly 0.0.  mean[i] and cov[i][i] are
+ *     the mean and var bytes of samsim_get_weighted_stats for the same slots and group, and count, sum_w and sum_w2 are its bytes
+ *     too; a slot has the bytes it would have alone.  The correlations are formed on the host (cov / sqrt(var_i var_j)).
+ *   Like every getter the calls wait for the handle's streams; they change neither the state, the status, the clock, the output
+ *     snapshot, the labels, the tracks, the scores nor the weight row.
+ *   Scratch.  samsim_get_weighted_covariance stays within SAMSIM_WEIGHT_SCRATCH_BYTES (its partials lie where those of the weighted
+ *     moments do).  samsim_get_weighted_profile_stats: at most SAMSIM_WPROFILE_SCRATCH_BYTES of device memory whatever ncol and the
+ *     request are (the waves' partials of one pass, then the results); allocated on first use, freed by samsim_destroy.
+ *   Not in scope.  Weighted profile histograms; all groups in one call; resampling or any write to the ensemble; weights in
+ *     checkpoint files.
+ *   Errors, all found before any device work, in this order; a call that is refused writes nothing to the caller's buffers.
+ *     samsim_get_weighted_profile_stats: SAMSIM_ERR_ARG for h, rq or out NULL; every check of samsim_get_profile_stats, in its order;
+ *     no weight row; the group checks of samsim_get_covariance.  samsim_get_weighted_covariance: SAMSIM_ERR_ARG for any NULL pointer;
+ *     nslots outside 1..SAMSIM_SENS_MAX_SLOTS; a bad slot; no weight row; the group checks. */
+#define SAMSIM_WPROFILE_SCRATCH_BYTES (4ull << 20)   /* 3.5 MiB of partials (1 024 waves x 64 bins x 56 bytes), then the results */
+int samsim_get_weighted_profile_stats(samsim_handle *h, const samsim_profile_request *rq, int32_t group,
+                                      samsim_wstat *out /*[narrays][nbins]*/);
+int samsim_get_weighted_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group,
+                                   int64_t *count, double *sum_w, double *sum_w2,
+                                   double *mean /*[nslots]*/, double *cov /*[nslots][nslots]*/);
 
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);

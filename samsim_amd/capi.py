@@ -573,6 +573,14 @@ class Solver:
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
+        # and the weighted profile statistics and the weighted covariances
+        wprof_sig = {"get_weighted_profile_stats": [vp, C.POINTER(ProfileRequest), C.c_int32, C.c_void_p],
+                     "get_weighted_covariance": [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]}
+        for n, a in wprof_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
 
     # -- API
     def set_forcing(self, fl_sw, fl_lw, T2m, precip, dT2m=None, precip_scale=None):
@@ -1067,6 +1075,46 @@ class Solver:
         with that label -- (samsim_get_weighted_histogram): float64 [nvbins+2]; capi.weighted_quantile_bracket reads quantiles off
         it"""
         return self.weighted_histogram_raw(_slot(name), hist_bins(nvbins, v0, dv), -1 if group is None else int(group))
+
+    def weighted_profile_stats_raw(self, rq: ProfileRequest, group=-1) -> np.ndarray:
+        """samsim_get_weighted_profile_stats with the arguments as given (no checks on this side): WSTAT_DTYPE [narrays][nbins]"""
+        out = np.zeros((max(0, min(rq.narrays, PROFILE_MAX_ARRAYS)), max(0, min(rq.nbins, PROFILE_MAX_BINS))), dtype=WSTAT_DTYPE)
+        buf = np.zeros(max(1, out.size), dtype=WSTAT_DTYPE)
+        self._chk(self._f("get_weighted_profile_stats")(self._h, C.byref(rq), int(group), buf.ctypes.data), "get_weighted_profile_stats")
+        out.ravel()[:] = buf[:out.size]
+        return out
+
+    def weighted_profile_stats(self, names, axis="layer", origin="top", nbins=None, z0=0.0, dz=None, group=None):
+        """{name: WSTAT_DTYPE array [nbins]}: per bin of profile_stats the count, sum_w, sum_w2, the weighted mean, the weighted
+        population variance, min and max of the bin value over the running columns with a positive weight that contribute to the
+        bin -- with group: of those with that label -- (samsim_get_weighted_profile_stats): the posterior profile with its spread;
+        sum_w^2 / sum_w2 is the effective sample size of a bin"""
+        names = list(names)
+        if axis == "depth" and (nbins is None or dz is None):
+            raise ValueError("axis='depth' needs nbins and dz")
+        rq = self._profile_request(names, axis, origin, nbins, z0, dz)
+        out = self.weighted_profile_stats_raw(rq, -1 if group is None else int(group))
+        return {n: out[i] for i, n in enumerate(names)}
+
+    def weighted_covariance_raw(self, slots, group=-1):
+        """samsim_get_weighted_covariance with the arguments as given (no checks on this side): (count, sum_w, sum_w2, mean [nslots],
+        cov [nslots, nslots])"""
+        slots = [int(x) for x in slots]
+        n = len(slots)
+        arr = (C.c_int32 * max(1, n))(*slots)
+        count, sum_w, sum_w2 = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        m = max(1, min(n, SENS_MAX_SLOTS))
+        mean, cov = np.zeros(m), np.zeros((m, m))
+        self._chk(self._f("get_weighted_covariance")(self._h, n, arr, int(group), C.byref(count), C.byref(sum_w), C.byref(sum_w2),
+                                                     mean.ctypes.data, cov.ctypes.data), "get_weighted_covariance")
+        return int(count.value), float(sum_w.value), float(sum_w2.value), mean, cov
+
+    def weighted_covariance(self, names, group=None):
+        """(count, sum_w, sum_w2, mean [n], cov [n, n]) of the slots `names` (from SCALARS, "N_active", or ints of track_slot,
+        func_slot, score_slot, weight_slot) over the running columns with a positive weight -- with group: of those with that label
+        -- (samsim_get_weighted_covariance): weighted means and weighted population covariances, the diagonal the variances of
+        weighted_stats; capi.correlation(cov) gives the correlations"""
+        return self.weighted_covariance_raw([_slot(n) for n in names], -1 if group is None else int(group))
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

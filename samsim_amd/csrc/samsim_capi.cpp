@@ -23,6 +23,7 @@
 #include "samsim_sens.h"
 #include "samsim_tracks.h"
 #include "samsim_weights.h"
+#include "samsim_wprofile.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
 // samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS) over every column
@@ -92,6 +93,7 @@ struct samsim_handle {
   samsim_sensor_spec sensor[SAMSIM_MAX_SENSORS]{};
   double *weight_row = nullptr; // [ncol] weights of the columns (samsim_set_weights), changed by that call alone
   void *d_weight = nullptr;    // samsim_set_weights and the weighted reductions: the waves' tables and partials, then the results (kWeightScratch bytes)
+  void *d_wprof = nullptr;     // samsim_get_weighted_profile_stats: the waves' partials of one pass, then the results (kWProfScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -253,6 +255,10 @@ static_assert((size_t)SAMSIM_SELECT_MAX_OUT * DEV_SEL_COLUMN_BYTES <= kStageByte
 constexpr size_t kWeightScratch = DEV_WEIGHT_BYTES;
 static_assert(kWeightScratch <= SAMSIM_WEIGHT_SCRATCH_BYTES && SAMSIM_WEIGHT_SCRATCH_BYTES <= (16ull << 20), "weight scratch bound of samsim.h");
 static_assert(sizeof(samsim_weight_spec) == 32 && sizeof(samsim_weight_info) == 40 && sizeof(samsim_wstat) == 56, "the weight structs of samsim.h");
+
+// device scratch of the weighted profile statistics: the waves' partials of one pass, then the results of the largest request
+constexpr size_t kWProfScratch = DEV_WPROF_BYTES;
+static_assert(kWProfScratch <= SAMSIM_WPROFILE_SCRATCH_BYTES && SAMSIM_WPROFILE_SCRATCH_BYTES <= (16ull << 20), "weighted profile scratch bound of samsim.h");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -633,7 +639,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens); (void)hipFree(h->tracks);
   (void)hipFree(h->func_rows);
   (void)hipFree(h->score_rows);
-  (void)hipFree(h->weight_row); (void)hipFree(h->d_weight);
+  (void)hipFree(h->weight_row); (void)hipFree(h->d_weight); (void)hipFree(h->d_wprof);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -1818,6 +1824,64 @@ int samsim_get_weighted_histogram(samsim_handle *h, int32_t slot, const samsim_h
                                      h->ncol, e, d_tables, d_out, h->stream));
   HIPCHK(hipMemcpyAsync(wsum, d_out, sizeof(double) * (size_t)(e.nvbins + 2), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_get_weighted_profile_stats(samsim_handle *h, const samsim_profile_request *rq, int32_t group, samsim_wstat *out) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !rq || !out) return SAMSIM_ERR_ARG;
+  int rc = check_profile_request(h, rq);
+  if (rc) return rc;
+  if (!h->weight_row) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  if (!h->d_wprof) HIPCHK(hipMalloc(&h->d_wprof, kWProfScratch));
+  WProfPartial *d_part = (WProfPartial *)h->d_wprof;
+  samsim_wstat *d_out = (samsim_wstat *)((char *)h->d_wprof + DEV_WPROF_PART_BYTES);
+  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
+  // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
+  // the next pass writes them
+  for (int i = 0; i < rq->narrays; ++i)
+    for (int b0 = 0; b0 < rq->nbins; b0 += DEV_PROF_BINS) {
+      const int nb = rq->nbins - b0 < DEV_PROF_BINS ? rq->nbins - b0 : DEV_PROF_BINS;
+      HIPCHK(samsim_launch_weighted_profile(h->lay, h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol,
+                                            h->cfg.nlayer, rq->axis, rq->origin, rq->arrays[i], b0, nb, rq->nbins, depth ? rq->z0 : 0.0,
+                                            depth ? rq->dz : 1.0, d_part, d_out + (size_t)i * rq->nbins + b0, h->stream));
+    }
+  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_wstat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_get_weighted_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group, int64_t *count, double *sum_w,
+                                   double *sum_w2, double *mean, double *cov) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !slots || !count || !sum_w || !sum_w2 || !mean || !cov) return SAMSIM_ERR_ARG;
+  if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < nslots; ++i)
+    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
+  if (!h->weight_row) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  rc = func_refresh_for(h, nslots, slots);
+  if (rc) return rc;
+  if (!h->d_weight) HIPCHK(hipMalloc(&h->d_weight, kWeightScratch));
+  double *d_part = (double *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
+  WCovResult *d_out = (WCovResult *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
+  SensRows rows{};
+  for (int i = 0; i < nslots; ++i) rows.row[i] = slot_row(h, slots[i]);
+  HIPCHK(samsim_launch_weighted_covariance(rows, nslots, h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group,
+                                           h->ncol, d_part, d_out, h->stream));
+  WCovResult res;
+  HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(WCovResult), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *count = res.count;
+  *sum_w = res.sum_w;
+  *sum_w2 = res.sum_w2;
+  std::memcpy(mean, res.mean, sizeof(double) * (size_t)nslots);
+  std::memcpy(cov, res.cov, sizeof(double) * (size_t)nslots * (size_t)nslots);
   return SAMSIM_OK;
 }
 

@@ -1,6 +1,6 @@
 // samsim_weights.h -- what samsim_weights.hip and the C-ABI host code share about the weight row and the weighted reductions
-// (samsim_set_weights, samsim_get_weighted_stats, samsim_get_weighted_histogram, include/samsim.h).  The step kernel does not
-// include this header.
+// (samsim_set_weights, samsim_get_weighted_stats, samsim_get_weighted_histogram, samsim_get_weighted_covariance, include/samsim.h).
+// The step kernel does not include this header.
 #ifndef SAMSIM_WEIGHTS_H
 #define SAMSIM_WEIGHTS_H
 
@@ -34,6 +34,21 @@ static_assert(sizeof(samsim_wstat) * SAMSIM_SENS_MAX_SLOTS <= DEV_WEIGHT_RESULT_
 #define DEV_WEIGHT_BYTES (DEV_WEIGHT_RESULT_AT + DEV_WEIGHT_RESULT_BYTES)
 static_assert(DEV_WEIGHT_BYTES <= SAMSIM_WEIGHT_SCRATCH_BYTES, "weight scratch bound of samsim.h");
 
+// samsim_get_weighted_covariance.  A wave's partial is DEV_WCOV_PART doubles whatever nslots is: n (a count below 2^53 is exact in a
+// double), W, W2, the weighted means of the slots, the weighted co-moments of the pairs (i, j), i <= j, row by row of the upper
+// triangle of nslots slots.  The partials lie where those of the weighted moments do, the result where theirs does.
+#define DEV_WCOV_MEAN0 3
+#define DEV_WCOV_C0 (3 + SAMSIM_SENS_MAX_SLOTS)
+#define DEV_WCOV_PART (3 + SAMSIM_SENS_MAX_SLOTS + DEV_SENS_PAIRS)
+struct WCovResult {
+  long long count;
+  double sum_w, sum_w2;
+  double mean[SAMSIM_SENS_MAX_SLOTS];
+  double cov[SAMSIM_SENS_MAX_SLOTS * SAMSIM_SENS_MAX_SLOTS];
+};
+static_assert(sizeof(double) * DEV_WCOV_PART * DEV_WEIGHT_GRID <= DEV_WEIGHT_PART_BYTES, "the covariance partials fit where the moments' do");
+static_assert(sizeof(WCovResult) <= DEV_WEIGHT_RESULT_BYTES, "the covariance result fits where a histogram row does");
+
 // samsim_weights.hip.  x: the [ncol] row of the source slot, or null for n_active.  labels: null (every column with status 0 is
 // IN), or the label row of samsim_set_groups, of which only the columns with label `group` are.  part and out lie in the handle's
 // scratch; the calls only enqueue.
@@ -50,5 +65,9 @@ extern "C" hipError_t samsim_launch_weighted_stats(SensRows rows, int nslots, co
 extern "C" hipError_t samsim_launch_weighted_hist(const double *x, const double *w, const int32_t *n_active, const int32_t *status,
                                                   const int32_t *labels, int group, long long ncol, HistEdges e, double *tables, double *out,
                                                   hipStream_t stream);
+// the weighted means and covariances of the nslots rows over the same columns, in one walk: part [grid][DEV_WCOV_PART]
+extern "C" hipError_t samsim_launch_weighted_covariance(SensRows rows, int nslots, const double *w, const int32_t *n_active,
+                                                        const int32_t *status, const int32_t *labels, int group, long long ncol,
+                                                        double *part, WCovResult *out, hipStream_t stream);
 
 #endif

@@ -1,6 +1,6 @@
 // samsim_weights.hip -- the weight row of the ensemble and the reductions that take it (samsim_set_weights,
-// samsim_get_weighted_stats, samsim_get_weighted_histogram, include/samsim.h): posterior statistics with w ~ exp(-J / 2) formed and
-// applied on the device.
+// samsim_get_weighted_stats, samsim_get_weighted_histogram, samsim_get_weighted_covariance, include/samsim.h): posterior statistics
+// with w ~ exp(-J / 2) formed and applied on the device.
 //
 // Every kernel follows the unweighted reductions: one wave owns one 64-column block at a time (lane = column) and strides over the
 // blocks with a fixed grid; its loads of the rows, of status and of the labels are coalesced and the next block's are under way
@@ -10,6 +10,8 @@
 // them (lane l the waves [l * per, (l + 1) * per), then the lanes in order).
 // The weighted histogram adds a block's weights to the wave's LDS table in lane order -- ascending column order --, the lane that
 // owns an entry (entry mod 64) doing the addition, and a second kernel adds the waves' tables in the same bracketing.
+// The weighted covariances are the weighted moments with the co-moments of every pair of slots riding along: the same lane update,
+// the same lane-to-wave order and the same merge, so their diagonal is samsim_get_weighted_stats byte for byte.
 //
 // No atomics of any kind, no floating-point sum whose order depends on scheduling: two calls return the same bytes.  The kernels
 // read slots, status and labels and write the weight row and the handle's weight scratch, nothing else.
@@ -297,6 +299,146 @@ void launch_wstat(SensRows rows, const double *w, const int32_t *n_active, const
   hipLaunchKernelGGL(wstat_kernel<NS>, dim3(grid), dim3(64), 0, stream, rows, w, n_active, status, labels, group, ncol, part);
 }
 
+// ------------------------------------------------------------------------------------------------------ weighted covariances
+
+constexpr int kLaneStride = 65;   // doubles from one quantity's 64 lane values to the next in LDS
+
+// Running weighted moments of one pair of slots (i, j): n columns of total weight W, the two weighted means, the weighted sum of
+// products of deviations.  WRun::merge with a second variable: for i == j every operation is that of WRun::merge on m2, and every
+// update is symmetric in i and j down to the bits, so a slot listed twice gives the bytes of its variance.
+struct WPairAcc {
+  long long n;
+  double W, W2, mi, mj, c;
+  // the cross term is delta_i delta_j W_a W_b / W; b is not empty
+  __device__ __forceinline__ void add(long long nb, double W_b, double W2_b, double mi_b, double mj_b, double c_b) {
+    if (n == 0) {
+      n = nb; W = W_b; W2 = W2_b; mi = mi_b; mj = mj_b; c = c_b;
+      return;
+    }
+    const double Wn = W + W_b;
+    const double di = mi_b - mi, dj = mj_b - mj;
+    const double fb = W_b / Wn;
+    mi = mi + di * fb;
+    mj = mj + dj * fb;
+    c = c + c_b + di * dj * (W * fb);
+    W = Wn;
+    W2 = W2 + W2_b;
+    n += nb;
+  }
+};
+
+// pair p of the upper triangle of ns slots, row by row: (0,0), (0,1), .. (0,ns-1), (1,1), ..
+__device__ __forceinline__ void pair_of(int p, int ns, int &i, int &j) {
+  i = 0;
+  while (p >= ns - i) { p -= ns - i; ++i; }
+  j = i + p;
+}
+
+// One walk serves every slot and every pair of the request (a template on nslots: every index is a compile-time one).  A lane
+// applies WRun::push to the means -- West's update -- and C_ij += w * d_i * (x_j - mean_j) with mean_j already updated, which for
+// i == j is the m2 of WRun::push, operation for operation; then the 64 lanes in lane order through LDS, one thread per pair.
+template <int NS>
+__global__ void __launch_bounds__(64) wcov_kernel(SensRows rows, const double *__restrict__ w, const int32_t *__restrict__ n_active,
+                                                  const int32_t *__restrict__ status, const int32_t *__restrict__ labels, int group,
+                                                  long long ncol, double *__restrict__ part) {
+  constexpr int NP = NS * (NS + 1) / 2;
+  __shared__ double s[(3 + NS + NP) * kLaneStride];   // [n, W, W2, means, co-moments][lane]
+  const int lane = threadIdx.x;
+  const long long nblk = (ncol + 63) / 64;
+  long long n = 0;
+  double W = 0.0, W2 = 0.0, mean[NS], C[NP];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) mean[i] = 0.0;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) C[p] = 0.0;
+  bool ok, ok_next = false;
+  double wv, wv_next = 0.0, v[NS], v_next[NS];
+  load_slots<NS>(rows, w, n_active, status, labels, group, ncol, blockIdx.x, lane, ok, wv, v);
+  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    // the next block's loads are under way while this block is consumed
+    if (blk + gridDim.x < nblk) load_slots<NS>(rows, w, n_active, status, labels, group, ncol, blk + gridDim.x, lane, ok_next, wv_next, v_next);
+    if (ok) {
+      n += 1;
+      W = W + wv;
+      W2 = W2 + wv * wv;
+      double wd[NS], e[NS];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const double d = v[i] - mean[i];
+        mean[i] = mean[i] + d * (wv / W);
+        wd[i] = wv * d;
+        e[i] = v[i] - mean[i];
+      }
+      int p = 0;
+#pragma unroll
+      for (int i = 0; i < NS; ++i)
+#pragma unroll
+        for (int j = i; j < NS; ++j, ++p) C[p] = C[p] + wd[i] * e[j];
+    }
+    ok = ok_next; wv = wv_next;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) v[i] = v_next[i];
+  }
+  s[lane] = (double)n; s[kLaneStride + lane] = W; s[2 * kLaneStride + lane] = W2;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) s[(3 + i) * kLaneStride + lane] = mean[i];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) s[(3 + NS + p) * kLaneStride + lane] = C[p];
+  __syncthreads();
+  if (lane >= NP) return;
+  // the 64 lanes in lane order, one thread per pair of slots
+  int i, j;
+  pair_of(lane, NS, i, j);
+  WPairAcc acc{0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int l = 0; l < 64; ++l) {
+    const long long nb = (long long)s[l];
+    if (nb > 0)
+      acc.add(nb, s[kLaneStride + l], s[2 * kLaneStride + l], s[(3 + i) * kLaneStride + l], s[(3 + j) * kLaneStride + l],
+              s[(3 + NS + lane) * kLaneStride + l]);
+  }
+  double *mine = part + (size_t)blockIdx.x * DEV_WCOV_PART;
+  mine[DEV_WCOV_C0 + lane] = acc.c;
+  if (i == j) mine[DEV_WCOV_MEAN0 + i] = acc.mi;
+  if (lane == 0) { mine[0] = (double)acc.n; mine[1] = acc.W; mine[2] = acc.W2; }
+}
+
+// One workgroup per pair of slots: the waves' partials in wave order, bracketed as wstat_merge_kernel brackets them.  The pair
+// (i, j) goes to cov[i][j] and cov[j][i]: one value, stored twice.
+__global__ void __launch_bounds__(64) wcov_merge_kernel(const double *__restrict__ part, int nwaves, int ns, WCovResult *__restrict__ out) {
+  __shared__ double s_n[64], s_W[64], s_W2[64], s_mi[64], s_mj[64], s_c[64];
+  const int lane = threadIdx.x, p = blockIdx.x, per = waves_per_lane(nwaves);
+  int i, j;
+  pair_of(p, ns, i, j);
+  WPairAcc acc{0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int wv = lane * per; wv < (lane + 1) * per && wv < nwaves; ++wv) {
+    const double *q = part + (size_t)wv * DEV_WCOV_PART;
+    const long long nb = (long long)q[0];
+    if (nb > 0) acc.add(nb, q[1], q[2], q[DEV_WCOV_MEAN0 + i], q[DEV_WCOV_MEAN0 + j], q[DEV_WCOV_C0 + p]);
+  }
+  s_n[lane] = (double)acc.n; s_W[lane] = acc.W; s_W2[lane] = acc.W2; s_mi[lane] = acc.mi; s_mj[lane] = acc.mj; s_c[lane] = acc.c;
+  __syncthreads();
+  if (lane != 0) return;
+  for (int l = 1; l < 64; ++l) {
+    const long long nb = (long long)s_n[l];
+    if (nb > 0) acc.add(nb, s_W[l], s_W2[l], s_mi[l], s_mj[l], s_c[l]);
+  }
+  const double cov = acc.n > 0 ? acc.c / acc.W : 0.0;
+  out->cov[i * ns + j] = cov;
+  out->cov[j * ns + i] = cov;
+  if (i == j) out->mean[i] = acc.n > 0 ? acc.mi : 0.0;
+  if (p == 0) {
+    out->count = acc.n;
+    out->sum_w = acc.n > 0 ? acc.W : 0.0;
+    out->sum_w2 = acc.n > 0 ? acc.W2 : 0.0;
+  }
+}
+
+template <int NS>
+void launch_wcov(SensRows rows, const double *w, const int32_t *n_active, const int32_t *status, const int32_t *labels, int group,
+                 long long ncol, int grid, double *part, hipStream_t stream) {
+  hipLaunchKernelGGL(wcov_kernel<NS>, dim3(grid), dim3(64), 0, stream, rows, w, n_active, status, labels, group, ncol, part);
+}
+
 // -------------------------------------------------------------------------------------------------------- weighted histogram
 
 // lane i's value in every lane (i is the same in every lane)
@@ -408,5 +550,26 @@ extern "C" hipError_t samsim_launch_weighted_hist(const double *x, const double 
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(whist_merge_kernel, dim3(e.nvbins + 2), dim3(64), 0, stream, tables, grid, out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t samsim_launch_weighted_covariance(SensRows rows, int nslots, const double *w, const int32_t *n_active,
+                                                        const int32_t *status, const int32_t *labels, int group, long long ncol,
+                                                        double *part, WCovResult *out, hipStream_t stream) {
+  const int grid = grid_of(ncol);
+  switch (nslots) {
+    case 1: launch_wcov<1>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    case 2: launch_wcov<2>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    case 3: launch_wcov<3>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    case 4: launch_wcov<4>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    case 5: launch_wcov<5>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    case 6: launch_wcov<6>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    case 7: launch_wcov<7>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    case 8: launch_wcov<8>(rows, w, n_active, status, labels, group, ncol, grid, part, stream); break;
+    default: return hipErrorInvalidValue;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(wcov_merge_kernel, dim3(nslots * (nslots + 1) / 2), dim3(64), 0, stream, part, grid, nslots, out);
   return hipGetLastError();
 }
