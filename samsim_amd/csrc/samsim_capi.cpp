@@ -18,6 +18,7 @@
 #include "samsim_functionals.h"
 #include "samsim_groups.h"
 #include "samsim_hist.h"
+#include "samsim_pass_plan.h"
 #include "samsim_select.h"
 #include "samsim_sensors.h"
 #include "samsim_sens.h"
@@ -26,11 +27,6 @@
 #include "samsim_wprofile.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
-// samsim_profile.hip: one pass of samsim_get_profile_stats (one array, bins [b0, b0 + nb), nb <= DEV_PROF_BINS) over every column
-// (labels null) or over the columns with label `group`
-extern "C" hipError_t samsim_launch_profile(const double *lay, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                            int group, long long ncol, int N, int axis, int origin, int array, int b0, int nb, int nbins,
-                                            double z0, double dz, ProfPartial *part, samsim_stat *out, hipStream_t stream);
 
 namespace {
 
@@ -530,6 +526,48 @@ int func_refresh_for(samsim_handle *h, int32_t nslots, const int32_t *slots) {
   for (int i = 0; i < nslots; ++i)
     if (func_slot(slots[i])) return func_refresh(h);
   return SAMSIM_OK;
+}
+
+// one group per call: -1 every column, else a label of samsim_set_groups
+bool good_group(const samsim_handle *h, int32_t group) { return group == -1 || (group >= 0 && h->groups && group < h->ngroups); }
+// the label row a reduction over `group` reads: none where every column counts
+const int32_t *labels_for(const samsim_handle *h, int32_t group) { return group >= 0 ? h->groups : nullptr; }
+
+// a scratch buffer of the handle: allocated by the first call that needs it and kept
+hipError_t scratch(void **buf, size_t bytes) { return *buf ? hipSuccess : hipMalloc(buf, bytes); }
+
+// What the reductions over a list of slots do between their null checks and their launch, in the order samsim.h gives: the checks
+// of the list, of the weight row (weighted) and of the group -- nothing touches the device before the request is known to be
+// good --, then use(), the functionals the list names brought up to date, and the rows of the slots.
+int slot_rows(samsim_handle *h, int32_t nslots, const int32_t *slots, bool weighted, int32_t group, SensRows *rows) {
+  if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
+  for (int i = 0; i < nslots; ++i)
+    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
+  if (weighted && !h->weight_row) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  rc = func_refresh_for(h, nslots, slots);
+  if (rc) return rc;
+  for (int i = 0; i < nslots; ++i) rows->row[i] = slot_row(h, slots[i]);
+  return SAMSIM_OK;
+}
+
+// The passes of a profile request, enqueued in order on the handle's stream: one per requested array and chunk of `chunk` bins
+// (samsim_pass_plan.h), so a pass's merge has read the partials before the next pass writes them.  launch(pass, at) enqueues the
+// family's pass; at = the place of the pass's first bin among the results [narrays][nbins] of the request.
+template <class Launch>
+int for_each_pass(const samsim_handle *h, const samsim_profile_request *rq, int32_t group, int chunk, Launch launch) {
+  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
+  return pass_plan(rq->narrays, rq->nbins, chunk, rq->origin, [&](const PassSpan &s) -> int {
+    ProfPass p;
+    p.lay = h->lay; p.n_active = h->n_active; p.status = h->status; p.labels = labels_for(h, group);
+    p.ncol = h->ncol; p.z0 = depth ? rq->z0 : 0.0; p.dz = depth ? rq->dz : 1.0;
+    p.group = group; p.N = h->cfg.nlayer; p.axis = rq->axis; p.origin = rq->origin; p.array = rq->arrays[s.array];
+    p.b0 = s.b0; p.nb = s.nb; p.lead = s.lead;
+    HIPCHK(launch(p, (size_t)s.array * (size_t)rq->nbins + (size_t)s.b0));
+    return SAMSIM_OK;
+  });
 }
 
 }  // namespace
@@ -1036,7 +1074,7 @@ int samsim_get_ensemble_stats(samsim_handle *h, int32_t nslots, const int32_t *s
     if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
   rc = func_refresh_for(h, nslots, slots);
   if (rc) return rc;
-  if (!h->d_stat) HIPCHK(hipMalloc(&h->d_stat, sizeof(StatPartial) * kStatGrid));
+  HIPCHK(scratch(&h->d_stat, sizeof(StatPartial) * kStatGrid));
   StatPartial *d_part = (StatPartial *)h->d_stat;
   std::vector<StatPartial> part(kStatGrid);
   const long long nc = h->ncol;
@@ -1090,23 +1128,15 @@ static int profile_stats(samsim_handle *h, const samsim_profile_request *rq, boo
   if (!h || !rq || !out) return SAMSIM_ERR_ARG;
   int rc = check_profile_request(h, rq);
   if (rc) return rc;
-  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
   if (grouped && (!h->groups || group < 0 || group >= h->ngroups)) return SAMSIM_ERR_ARG;
   rc = use(h);
   if (rc) return rc;
-  if (!h->d_prof) HIPCHK(hipMalloc(&h->d_prof, kProfScratch));
+  HIPCHK(scratch(&h->d_prof, kProfScratch));
   ProfPartial *d_part = (ProfPartial *)h->d_prof;
   samsim_stat *d_out = (samsim_stat *)((char *)h->d_prof + kProfPartBytes);
-  const int32_t *labels = grouped ? h->groups : nullptr;
-  // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
-  // the next pass writes them
-  for (int i = 0; i < rq->narrays; ++i)
-    for (int b0 = 0; b0 < rq->nbins; b0 += DEV_PROF_BINS) {
-      const int nb = rq->nbins - b0 < DEV_PROF_BINS ? rq->nbins - b0 : DEV_PROF_BINS;
-      HIPCHK(samsim_launch_profile(h->lay, h->n_active, h->status, labels, group, h->ncol, h->cfg.nlayer, rq->axis, rq->origin,
-                                   rq->arrays[i], b0, nb, rq->nbins, depth ? rq->z0 : 0.0, depth ? rq->dz : 1.0, d_part,
-                                   d_out + (size_t)i * rq->nbins + b0, h->stream));
-    }
+  rc = for_each_pass(h, rq, grouped ? group : -1, DEV_PROF_BINS,
+                     [&](const ProfPass &p, size_t at) { return samsim_launch_profile(p, d_part, d_out + at, h->stream); });
+  if (rc) return rc;
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_stat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
@@ -1154,7 +1184,7 @@ int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slot
   if (rc) return rc;
   rc = func_refresh_for(h, nslots, slots);
   if (rc) return rc;
-  if (!h->d_group) HIPCHK(hipMalloc(&h->d_group, kGroupScratch));
+  HIPCHK(scratch(&h->d_group, kGroupScratch));
   GroupPartial *d_part = (GroupPartial *)h->d_group;
   samsim_stat *d_out = (samsim_stat *)((char *)h->d_group + kGroupPartBytes);
   const size_t ng = (size_t)h->ngroups;
@@ -1198,7 +1228,7 @@ int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins 
   if (rc) return rc;
   rc = func_refresh_for(h, 1, &slot);
   if (rc) return rc;
-  if (!h->d_hist) HIPCHK(hipMalloc(&h->d_hist, kHistScratch));
+  HIPCHK(scratch(&h->d_hist, kHistScratch));
   const int ng = by_group ? h->ngroups : 1;
   const size_t bytes = sizeof(int64_t) * (size_t)ng * (size_t)(e.nvbins + 2);
   const double *row = slot_row(h, slot);
@@ -1223,43 +1253,29 @@ int samsim_get_profile_histogram(samsim_handle *h, const samsim_profile_request 
   if (group < -1 || (group >= 0 && (!h->groups || group >= h->ngroups))) return SAMSIM_ERR_ARG;
   rc = use(h);
   if (rc) return rc;
-  if (!h->d_hist) HIPCHK(hipMalloc(&h->d_hist, kHistScratch));
-  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
+  HIPCHK(scratch(&h->d_hist, kHistScratch));
   const size_t bytes = sizeof(int64_t) * (size_t)rq->nbins * (size_t)(e.nvbins + 2);
-  const int chunk = dev_hist_chunk(e.nvbins);
   HIPCHK(hipMemsetAsync(h->d_hist, 0, bytes, h->stream));
-  // one pass per chunk of depth bins, all on the handle's stream; the passes add into disjoint rows of the counts
-  for (int b0 = 0; b0 < rq->nbins; b0 += chunk) {
-    const int nb = rq->nbins - b0 < chunk ? rq->nbins - b0 : chunk;
-    HIPCHK(samsim_launch_profile_hist(h->lay, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol, h->cfg.nlayer,
-                                      rq->axis, rq->origin, rq->arrays[0], b0, nb, rq->nbins, depth ? rq->z0 : 0.0, depth ? rq->dz : 1.0, e,
-                                      (unsigned long long *)h->d_hist, h->stream));
-  }
+  // the passes add into disjoint rows of the counts
+  rc = for_each_pass(h, rq, group, dev_hist_chunk(e.nvbins), [&](const ProfPass &p, size_t) {
+    return samsim_launch_profile_hist(p, e, (unsigned long long *)h->d_hist, h->stream);
+  });
+  if (rc) return rc;
   HIPCHK(hipMemcpyAsync(counts, h->d_hist, bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }
 
-// one group per call: -1 every column, else a label of samsim_set_groups
-static bool good_group(const samsim_handle *h, int32_t group) { return group == -1 || (group >= 0 && h->groups && group < h->ngroups); }
-
 int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group, int64_t *count, double *mean, double *cov) {
   // every check first: nothing below touches the device before the request is known to be good
   if (!h || !slots || !count || !mean || !cov) return SAMSIM_ERR_ARG;
-  if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
-  for (int i = 0; i < nslots; ++i)
-    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
-  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
-  int rc = use(h);
+  SensRows rows{};
+  const int rc = slot_rows(h, nslots, slots, false, group, &rows);
   if (rc) return rc;
-  rc = func_refresh_for(h, nslots, slots);
-  if (rc) return rc;
-  if (!h->d_sens) HIPCHK(hipMalloc(&h->d_sens, kSensScratch));
+  HIPCHK(scratch(&h->d_sens, kSensScratch));
   double *d_part = (double *)h->d_sens;
   CovResult *d_out = (CovResult *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
-  SensRows rows{};
-  for (int i = 0; i < nslots; ++i) rows.row[i] = slot_row(h, slots[i]);
-  HIPCHK(samsim_launch_covariance(rows, nslots, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol, d_part, d_out,
+  HIPCHK(samsim_launch_covariance(rows, nslots, h->n_active, h->status, labels_for(h, group), group, h->ncol, d_part, d_out,
                                   h->stream));
   CovResult res;
   HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(CovResult), hipMemcpyDeviceToHost, h->stream));
@@ -1282,20 +1298,14 @@ int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request
   if (rc) return rc;
   rc = func_refresh_for(h, 1, &predictor_slot);
   if (rc) return rc;
-  if (!h->d_sens) HIPCHK(hipMalloc(&h->d_sens, kSensScratch));
+  HIPCHK(scratch(&h->d_sens, kSensScratch));
   SensProfPartial *d_part = (SensProfPartial *)h->d_sens;
   samsim_pair_stat *d_out = (samsim_pair_stat *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
-  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
   const double *x = slot_row(h, predictor_slot);
-  // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
-  // the next pass writes them
-  for (int i = 0; i < rq->narrays; ++i)
-    for (int b0 = 0; b0 < rq->nbins; b0 += DEV_PROF_BINS) {
-      const int nb = rq->nbins - b0 < DEV_PROF_BINS ? rq->nbins - b0 : DEV_PROF_BINS;
-      HIPCHK(samsim_launch_profile_regression(h->lay, x, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol,
-                                              h->cfg.nlayer, rq->axis, rq->origin, rq->arrays[i], b0, nb, rq->nbins, depth ? rq->z0 : 0.0,
-                                              depth ? rq->dz : 1.0, d_part, d_out + (size_t)i * rq->nbins + b0, h->stream));
-    }
+  rc = for_each_pass(h, rq, group, DEV_PROF_BINS, [&](const ProfPass &p, size_t at) {
+    return samsim_launch_profile_regression(p, x, d_part, d_out + at, h->stream);
+  });
+  if (rc) return rc;
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_pair_stat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
@@ -1434,12 +1444,12 @@ int samsim_select_columns(samsim_handle *h, const samsim_selection *sel, int64_t
   if (rc) return rc;
   for (int i = 0; i < sel->nterms && !rc; ++i) rc = func_refresh_for(h, 1, &sel->terms[i].slot);
   if (rc) return rc;
-  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
+  HIPCHK(scratch(&h->d_select, kSelectScratch));
   SelParams p{};
   for (int i = 0; i < sel->nterms; ++i) p.t[i] = SelTerm{slot_row(h, sel->terms[i].slot), sel->terms[i].lo, sel->terms[i].hi};
   p.n_active = h->n_active;
   p.status = sel->status_mode == SAMSIM_SELECT_ANY ? nullptr : h->status;
-  p.labels = sel->group >= 0 ? h->groups : nullptr;
+  p.labels = labels_for(h, sel->group);
   p.ncol = h->ncol;
   // wave w owns the blocks [w * per, (w + 1) * per): as many waves as that leaves with a block, DEV_SEL_GRID at most
   const long long nblk = (h->ncol + 63) / 64;
@@ -1466,7 +1476,7 @@ static int stage_list(samsim_handle *h, int64_t ncols, const int64_t *cols, long
     if (cols[j] < 0 || cols[j] >= h->ncol) return SAMSIM_ERR_ARG;
   int rc = use(h);
   if (rc) return rc;
-  if (!h->d_select) HIPCHK(hipMalloc(&h->d_select, kSelectScratch));
+  HIPCHK(scratch(&h->d_select, kSelectScratch));
   *d_cols = (long long *)((char *)h->d_select + DEV_SEL_LIST_AT);
   HIPCHK(hipMemcpyAsync(*d_cols, cols, sizeof(int64_t) * (size_t)ncols, hipMemcpyHostToDevice, h->stream));
   return SAMSIM_OK;
@@ -1665,7 +1675,7 @@ int samsim_score(samsim_handle *h, const double *obs, const double *weight, int3
   SensorParams p{};
   sensor_params(h, &p);
   p.out = h->score_rows;
-  p.labels = group >= 0 ? h->groups : nullptr;
+  p.labels = labels_for(h, group);
   p.group = group;
   for (int i = 0; i < h->nsensors; ++i) {
     const bool have = !std::isnan(obs[i]);
@@ -1749,7 +1759,7 @@ int samsim_set_weights(samsim_handle *h, const samsim_weight_spec *spec, samsim_
   }
   const bool fresh = !h->weight_row;
   rc = func_refresh_for(h, 1, &spec->slot);
-  if (!rc && !h->d_weight && !hip_ok(hipMalloc(&h->d_weight, kWeightScratch), "hipMalloc weight scratch")) rc = SAMSIM_ERR_HIP;
+  if (!rc && !hip_ok(scratch(&h->d_weight, kWeightScratch), "hipMalloc weight scratch")) rc = SAMSIM_ERR_HIP;
   if (rc) {
     if (fresh) (void)hipFree(row);
     return rc;
@@ -1758,7 +1768,7 @@ int samsim_set_weights(samsim_handle *h, const samsim_weight_spec *spec, samsim_
   WeightPartial *d_part = (WeightPartial *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
   WeightPartial *d_out = (WeightPartial *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
   const double c = spec->kind == SAMSIM_WEIGHT_GAUSS ? 0.5 / spec->scale : 0.0;
-  HIPCHK(samsim_launch_set_weights(slot_row(h, spec->slot), h->n_active, h->status, spec->group >= 0 ? h->groups : nullptr, spec->group,
+  HIPCHK(samsim_launch_set_weights(slot_row(h, spec->slot), h->n_active, h->status, labels_for(h, spec->group), spec->group,
                                    h->ncol, spec->kind, c, row, d_part, d_out, h->stream));
   WeightPartial res;
   HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(WeightPartial), hipMemcpyDeviceToHost, h->stream));
@@ -1783,21 +1793,13 @@ int samsim_get_weights(samsim_handle *h, int64_t col0, int64_t ncols, double *ou
 int samsim_get_weighted_stats(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group, samsim_wstat *out) {
   // every check first: nothing below touches the device before the request is known to be good
   if (!h || !slots || !out) return SAMSIM_ERR_ARG;
-  if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
-  for (int i = 0; i < nslots; ++i)
-    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
-  if (!h->weight_row) return SAMSIM_ERR_ARG;
-  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
-  int rc = use(h);
+  SensRows rows{};
+  const int rc = slot_rows(h, nslots, slots, true, group, &rows);
   if (rc) return rc;
-  rc = func_refresh_for(h, nslots, slots);
-  if (rc) return rc;
-  if (!h->d_weight) HIPCHK(hipMalloc(&h->d_weight, kWeightScratch));
+  HIPCHK(scratch(&h->d_weight, kWeightScratch));
   WStatPartial *d_part = (WStatPartial *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
   samsim_wstat *d_out = (samsim_wstat *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
-  SensRows rows{};
-  for (int i = 0; i < nslots; ++i) rows.row[i] = slot_row(h, slots[i]);
-  HIPCHK(samsim_launch_weighted_stats(rows, nslots, h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol,
+  HIPCHK(samsim_launch_weighted_stats(rows, nslots, h->weight_row, h->n_active, h->status, labels_for(h, group), group, h->ncol,
                                       d_part, d_out, h->stream));
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_wstat) * (size_t)nslots, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1817,10 +1819,10 @@ int samsim_get_weighted_histogram(samsim_handle *h, int32_t slot, const samsim_h
   if (rc) return rc;
   rc = func_refresh_for(h, 1, &slot);
   if (rc) return rc;
-  if (!h->d_weight) HIPCHK(hipMalloc(&h->d_weight, kWeightScratch));
+  HIPCHK(scratch(&h->d_weight, kWeightScratch));
   double *d_tables = (double *)((char *)h->d_weight + DEV_WEIGHT_TABLES_AT);
   double *d_out = (double *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
-  HIPCHK(samsim_launch_weighted_hist(slot_row(h, slot), h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group,
+  HIPCHK(samsim_launch_weighted_hist(slot_row(h, slot), h->weight_row, h->n_active, h->status, labels_for(h, group), group,
                                      h->ncol, e, d_tables, d_out, h->stream));
   HIPCHK(hipMemcpyAsync(wsum, d_out, sizeof(double) * (size_t)(e.nvbins + 2), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1836,19 +1838,13 @@ int samsim_get_weighted_profile_stats(samsim_handle *h, const samsim_profile_req
   if (!good_group(h, group)) return SAMSIM_ERR_ARG;
   rc = use(h);
   if (rc) return rc;
-  if (!h->d_wprof) HIPCHK(hipMalloc(&h->d_wprof, kWProfScratch));
+  HIPCHK(scratch(&h->d_wprof, kWProfScratch));
   WProfPartial *d_part = (WProfPartial *)h->d_wprof;
   samsim_wstat *d_out = (samsim_wstat *)((char *)h->d_wprof + DEV_WPROF_PART_BYTES);
-  const bool depth = rq->axis == SAMSIM_PROFILE_BY_DEPTH;
-  // one pass per array and chunk of DEV_PROF_BINS bins, all on the handle's stream: a pass's merge has read the partials before
-  // the next pass writes them
-  for (int i = 0; i < rq->narrays; ++i)
-    for (int b0 = 0; b0 < rq->nbins; b0 += DEV_PROF_BINS) {
-      const int nb = rq->nbins - b0 < DEV_PROF_BINS ? rq->nbins - b0 : DEV_PROF_BINS;
-      HIPCHK(samsim_launch_weighted_profile(h->lay, h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group, h->ncol,
-                                            h->cfg.nlayer, rq->axis, rq->origin, rq->arrays[i], b0, nb, rq->nbins, depth ? rq->z0 : 0.0,
-                                            depth ? rq->dz : 1.0, d_part, d_out + (size_t)i * rq->nbins + b0, h->stream));
-    }
+  rc = for_each_pass(h, rq, group, DEV_PROF_BINS, [&](const ProfPass &p, size_t at) {
+    return samsim_launch_weighted_profile(p, h->weight_row, d_part, d_out + at, h->stream);
+  });
+  if (rc) return rc;
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_wstat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
@@ -1858,21 +1854,13 @@ int samsim_get_weighted_covariance(samsim_handle *h, int32_t nslots, const int32
                                    double *sum_w2, double *mean, double *cov) {
   // every check first: nothing below touches the device before the request is known to be good
   if (!h || !slots || !count || !sum_w || !sum_w2 || !mean || !cov) return SAMSIM_ERR_ARG;
-  if (nslots < 1 || nslots > SAMSIM_SENS_MAX_SLOTS) return SAMSIM_ERR_ARG;
-  for (int i = 0; i < nslots; ++i)
-    if (!good_slot(h, slots[i])) return SAMSIM_ERR_ARG;
-  if (!h->weight_row) return SAMSIM_ERR_ARG;
-  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
-  int rc = use(h);
+  SensRows rows{};
+  const int rc = slot_rows(h, nslots, slots, true, group, &rows);
   if (rc) return rc;
-  rc = func_refresh_for(h, nslots, slots);
-  if (rc) return rc;
-  if (!h->d_weight) HIPCHK(hipMalloc(&h->d_weight, kWeightScratch));
+  HIPCHK(scratch(&h->d_weight, kWeightScratch));
   double *d_part = (double *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
   WCovResult *d_out = (WCovResult *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
-  SensRows rows{};
-  for (int i = 0; i < nslots; ++i) rows.row[i] = slot_row(h, slots[i]);
-  HIPCHK(samsim_launch_weighted_covariance(rows, nslots, h->weight_row, h->n_active, h->status, group >= 0 ? h->groups : nullptr, group,
+  HIPCHK(samsim_launch_weighted_covariance(rows, nslots, h->weight_row, h->n_active, h->status, labels_for(h, group), group,
                                            h->ncol, d_part, d_out, h->stream));
   WCovResult res;
   HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(WCovResult), hipMemcpyDeviceToHost, h->stream));

@@ -110,10 +110,9 @@ struct DevParams {
   double p17, p14, tf_c3;
 };
 
-// samsim_get_profile_stats (samsim_profile.hip): one pass reduces one array over at most DEV_PROF_BINS bins with a fixed grid of at
+// samsim_get_profile_stats (samsim_profile.h): one pass reduces one array over at most DEV_PROF_BINS bins with a fixed grid of at
 // most DEV_PROF_GRID one-wave workgroups; every wave leaves one partial per bin, merged in wave order
 #define DEV_PROF_GRID 1024
 #define DEV_PROF_BINS 64
-struct ProfPartial { double mean, m2, mn, mx; long long n; };
 
 #endif

@@ -5,7 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
-#include "samsim_device.h"
+#include "samsim_pass_plan.h"
+#include "samsim_profile.h"
 
 // A row of counts has W = nvbins + 2 entries.  Both reductions run a fixed grid of at most DEV_HIST_GRID one-wave workgroups; a
 // wave counts in 32-bit entries of an LDS table and adds what it found to the 64-bit result table in device memory with integer
@@ -23,13 +24,7 @@ static inline bool dev_hist_in_lds(int ngroups, int nvbins) { return (long long)
 // lanes' rows over the banks); together at most the 64 KiB a workgroup gets without an opt-in.  Up to 121 value bins a pass
 // serves 64 depth bins as the statistics do, at SAMSIM_HIST_MAX_VBINS (254) 42.  Cost: passes = ceil(nbins / chunk), each a walk over
 // the layers of every column as in samsim_get_profile_stats.
-#define DEV_HIST_LDS_BYTES (64 << 10)
-static inline int dev_hist_row_stride(int nvbins) { return (nvbins + 2) | 1; }
-static inline int dev_hist_chunk(int nvbins) {
-  const int per_bin = (DEV_PROF_BINS + 1) * (int)sizeof(double) + dev_hist_row_stride(nvbins) * (int)sizeof(uint32_t);
-  const int c = (DEV_HIST_LDS_BYTES - 64 * (int)sizeof(unsigned long long)) / per_bin;
-  return c < DEV_PROF_BINS ? c : DEV_PROF_BINS;
-}
+// (DEV_HIST_LDS_BYTES, dev_hist_row_stride and dev_hist_chunk: samsim_pass_plan.h, where the host test of the passes reaches them)
 static inline size_t dev_hist_profile_lds(int nvbins) {
   const size_t c = (size_t)dev_hist_chunk(nvbins);
   return c * (DEV_PROF_BINS + 1) * sizeof(double) + 64 * sizeof(unsigned long long) + c * dev_hist_row_stride(nvbins) * sizeof(uint32_t);
@@ -55,10 +50,7 @@ __device__ __forceinline__ int hist_entry(double v, const HistEdges &e) {
 // status 0 --, counts[ngroups][W].
 extern "C" hipError_t samsim_launch_hist(const double *row, const int32_t *n_active, const int32_t *status, const int32_t *labels,
                                          long long ncol, int ngroups, HistEdges e, unsigned long long *counts, hipStream_t stream);
-// Profiles, one pass: bins [b0, b0 + nb) of the request's nbins with nb <= dev_hist_chunk(nvbins), rows b0 .. b0+nb-1 of
-// counts[nbins][W].  labels: null (every column counts), or the label row of which only the columns with label `group` count.
-extern "C" hipError_t samsim_launch_profile_hist(const double *lay, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                                 int group, long long ncol, int N, int axis, int origin, int array, int b0, int nb, int nbins,
-                                                 double z0, double dz, HistEdges e, unsigned long long *counts, hipStream_t stream);
+// Profiles, one pass (samsim_profile.h) with nb <= dev_hist_chunk(nvbins): rows b0 .. b0+nb-1 of counts[nbins][W].
+extern "C" hipError_t samsim_launch_profile_hist(ProfPass p, HistEdges e, unsigned long long *counts, hipStream_t stream);
 
 #endif

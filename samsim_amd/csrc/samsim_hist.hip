@@ -4,7 +4,7 @@
 //
 // Scalars: one wave owns one 64-column block at a time (lane = column) and strides over the blocks with a fixed grid, as
 // group_stats_kernel does; its loads of the row, of status and of the labels are coalesced and the next block's are under way while
-// this block is counted.  Profiles: the block walk of the profile statistics (samsim_profile_walk.h) fills the LDS tile [bin][lane];
+// this block is counted.  Profiles: a pass of samsim_profile.h, whose walk (samsim_profile_walk.h) fills the LDS tile [bin][lane];
 // then lane j walks row j of the tile and increments its own row of the count table -- no atomics in the loop.  Either way a wave
 // counts in 32-bit LDS entries and adds its table to the 64-bit result with integer atomics at the end (samsim_hist.h); there is no
 // floating-point atomic and no floating-point sum at all, so two calls return the same bytes.
@@ -102,6 +102,8 @@ __device__ __forceinline__ void flush_rows(const uint32_t *table, int stride, in
   for (int r = 0; r < nb; ++r) flush_table(table + r * stride, W, lane, out + (size_t)r * W);
 }
 
+// The layer / depth pair as it was before the pass descriptor: hist_profile_kernel<AXIS>(ProfPass, ...) measured 0.7 % slower at
+// 254 value bins (docs/HISTORY.md, "Profile reductions: one pass descriptor"), so this family keeps its two kernels.
 __global__ void __launch_bounds__(64) hist_layer_kernel(const double *__restrict__ lay, const int32_t *__restrict__ n_active,
                                                         const int32_t *__restrict__ status, const int32_t *__restrict__ labels, int group,
                                                         long long ncol, int N, int origin, int array, int b0, int nb, int chunk,
@@ -150,19 +152,16 @@ extern "C" hipError_t samsim_launch_hist(const double *row, const int32_t *n_act
   return hipGetLastError();
 }
 
-extern "C" hipError_t samsim_launch_profile_hist(const double *lay, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                                 int group, long long ncol, int N, int axis, int origin, int array, int b0, int nb, int nbins,
-                                                 double z0, double dz, HistEdges e, unsigned long long *counts, hipStream_t stream) {
-  const long long nblk = (ncol + 63) / 64;
-  const int grid = (int)(nblk < DEV_HIST_GRID ? nblk : DEV_HIST_GRID);
+extern "C" hipError_t samsim_launch_profile_hist(ProfPass p, HistEdges e, unsigned long long *counts, hipStream_t stream) {
   const int chunk = dev_hist_chunk(e.nvbins);
   const size_t lds = dev_hist_profile_lds(e.nvbins);
-  if (nb > chunk || lds > DEV_HIST_LDS_BYTES) return hipErrorInvalidValue;
-  if (axis == SAMSIM_PROFILE_BY_LAYER)
-    hipLaunchKernelGGL(hist_layer_kernel, dim3(grid), dim3(64), lds, stream, lay, n_active, status, labels, group, ncol, N, origin, array, b0,
-                       nb, chunk, e, counts);
+  const int grid = pass_grid(p, DEV_HIST_GRID, chunk);
+  if (!grid || lds > DEV_HIST_LDS_BYTES) return hipErrorInvalidValue;
+  if (p.axis == SAMSIM_PROFILE_BY_LAYER)
+    hipLaunchKernelGGL(hist_layer_kernel, dim3(grid), dim3(64), lds, stream, p.lay, p.n_active, p.status, p.labels, p.group, p.ncol, p.N,
+                       p.origin, p.array, p.b0, p.nb, chunk, e, counts);
   else
-    hipLaunchKernelGGL(hist_depth_kernel, dim3(grid), dim3(64), lds, stream, lay, n_active, status, labels, group, ncol, N, origin, array, b0,
-                       nb, chunk, origin == SAMSIM_PROFILE_FROM_TOP ? b0 > 0 : b0 + nb < nbins, z0, dz, e, counts);
+    hipLaunchKernelGGL(hist_depth_kernel, dim3(grid), dim3(64), lds, stream, p.lay, p.n_active, p.status, p.labels, p.group, p.ncol, p.N,
+                       p.origin, p.array, p.b0, p.nb, chunk, p.lead, p.z0, p.dz, e, counts);
   return hipGetLastError();
 }

@@ -1,9 +1,9 @@
 // samsim_profile_walk.h -- how one wave walks the layers of one 64-column block and finds every column's value in every bin of a
-// profile request (include/samsim.h, samsim_get_profile_stats): shared by the statistics (samsim_profile.hip) and the joint
-// histograms (samsim_hist.hip), which differ only in what they do with the finished values.  The step kernel does not include
-// this header.
+// profile request (include/samsim.h, samsim_get_profile_stats): shared by the four reductions of samsim_profile.h, which differ only
+// in what they do with the finished values.  The step kernel does not include this header.
 //
-// A walk serves one requested array and the bins [b0, b0 + nb) of the request, nb <= 64, for one block (lane = column).  It reads
+// A walk serves one pass (ProfPass): one requested array and the bins [b0, b0 + nb) of the request, nb <= 64, for one block
+// (lane = column), through walk_block<AXIS>.  It reads
 // 512-byte rows from the device layout [block][layer][array][64]; only the rows the request needs are touched (the array itself --
 // S_abs and m for S_bu -- and thick for the depth axis), and the rows of kAhead layers are requested before the first is waited
 // for.  Every lane moves through the bins of its own column monotonically and hands each finished bin value to the sink:
@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "samsim_column_read.h"
+#include "samsim_profile.h"
 
 namespace profile_walk {
 
@@ -58,6 +59,9 @@ __device__ __forceinline__ int active_layers(const int32_t *n_active, const int3
   if (col >= ncol || status[col] != 0) return 0;
   if (labels && labels[col] != group) return 0;
   return layers_within(n_active[col], N);
+}
+__device__ __forceinline__ int active_layers(const ProfPass &p, long long blk, int lane) {
+  return active_layers(p.n_active, p.status, p.labels, p.group, p.ncol, blk, lane, p.N);
 }
 
 // ---- layer axis: bin b holds layer b+1 (from the top) or layer N_active-b (from the bottom); bins [b0, b0+nb) of block blk,
@@ -155,6 +159,13 @@ __device__ __forceinline__ void depth_block(const double *__restrict__ lay, long
     }
   }
   if (cur >= b0 && cur < b0 + nb && L > 0.0) sink.put(cur - b0, W / L);   // the bin in which the column ends
+}
+
+// the walk of the pass's axis, chosen at compile time: a family's kernel is one template over AXIS
+template <int AXIS, class Sink>
+__device__ __forceinline__ void walk_block(const ProfPass &p, long long blk, int lane, int na, Sink &sink) {
+  if (AXIS == SAMSIM_PROFILE_BY_LAYER) layer_block(p.lay, p.ncol, p.N, blk, lane, na, p.origin, p.array, p.b0, p.nb, sink);
+  else depth_block(p.lay, p.ncol, p.N, blk, lane, na, p.origin, p.array, p.b0, p.nb, p.lead, p.z0, p.dz, sink);
 }
 
 }  // namespace profile_walk

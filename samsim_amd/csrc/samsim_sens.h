@@ -5,7 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "samsim_device.h"
+#include "samsim_profile.h"
 
 // Both reductions run a fixed grid of at most DEV_SENS_GRID one-wave workgroups (a wave per 64-column block at a time), fixed by
 // ncol alone; every wave leaves one partial, merged in wave order.
@@ -45,11 +45,8 @@ static_assert(4 * DEV_SENS_PROFILE_LDS <= (160u << 10), "four regression workgro
 extern "C" hipError_t samsim_launch_covariance(SensRows rows, int nslots, const int32_t *n_active, const int32_t *status,
                                                const int32_t *labels, int group, long long ncol, double *part, CovResult *out,
                                                hipStream_t stream);
-// one pass: array `array`, bins [b0, b0 + nb) of the request's nbins, nb <= DEV_PROF_BINS, results to out[0 .. nb); x: the
-// predictor's [ncol] row, or null for n_active
-extern "C" hipError_t samsim_launch_profile_regression(const double *lay, const double *x, const int32_t *n_active, const int32_t *status,
-                                                       const int32_t *labels, int group, long long ncol, int N, int axis, int origin,
-                                                       int array, int b0, int nb, int nbins, double z0, double dz, SensProfPartial *part,
-                                                       samsim_pair_stat *out, hipStream_t stream);
+// one pass (samsim_profile.h), results to out[0 .. nb); x: the predictor's [ncol] row, or null for n_active
+extern "C" hipError_t samsim_launch_profile_regression(ProfPass p, const double *x, SensProfPartial *part, samsim_pair_stat *out,
+                                                       hipStream_t stream);
 
 #endif

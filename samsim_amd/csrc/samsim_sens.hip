@@ -9,7 +9,7 @@
 // lanes are combined in lane order through LDS (Chan's pairwise update), one thread per pair of slots, and the wave's partial is
 // stored; cov_merge_kernel combines the waves' partials in wave order.
 //
-// Profiles: the block walk of the profile statistics (samsim_profile_walk.h) fills the LDS tile [bin][lane]; the block's 64
+// Profiles: a pass of samsim_profile.h, whose walk (samsim_profile_walk.h) fills the LDS tile [bin][lane]; the block's 64
 // predictor values lie beside it, and lane j folds row j with the statistics' own fold and merge (samsim_profile_fold.h) with the
 // predictor riding along.
 //
@@ -184,6 +184,8 @@ __device__ __forceinline__ void store_partials(SensProfPartial *part, int lane, 
   part[(size_t)blockIdx.x * DEV_PROF_BINS + lane] = p;
 }
 
+// The layer / depth pair as it was before the pass descriptor: sens_profile_kernel<AXIS>(ProfPass, ...) measured 2.3 % slower on
+// the depth axis (docs/HISTORY.md, "Profile reductions: one pass descriptor"), so this family keeps its two kernels.
 // ---- layer axis (profile_walk::layer_block): bins [b0, b0+nb)
 __global__ void __launch_bounds__(64) sens_layer_kernel(const double *__restrict__ lay, const double *__restrict__ x,
                                                         const int32_t *__restrict__ n_active, const int32_t *__restrict__ status,
@@ -278,21 +280,18 @@ extern "C" hipError_t samsim_launch_covariance(SensRows rows, int nslots, const 
   return hipGetLastError();
 }
 
-extern "C" hipError_t samsim_launch_profile_regression(const double *lay, const double *x, const int32_t *n_active, const int32_t *status,
-                                                       const int32_t *labels, int group, long long ncol, int N, int axis, int origin,
-                                                       int array, int b0, int nb, int nbins, double z0, double dz, SensProfPartial *part,
-                                                       samsim_pair_stat *out, hipStream_t stream) {
-  const long long nblk = (ncol + 63) / 64;
-  const int grid = (int)(nblk < DEV_SENS_GRID ? nblk : DEV_SENS_GRID);
-  if (nb < 1 || nb > DEV_PROF_BINS) return hipErrorInvalidValue;
-  if (axis == SAMSIM_PROFILE_BY_LAYER)
-    hipLaunchKernelGGL(sens_layer_kernel, dim3(grid), dim3(64), 0, stream, lay, x, n_active, status, labels, group, ncol, N, origin, array, b0,
-                       nb, part);
+extern "C" hipError_t samsim_launch_profile_regression(ProfPass p, const double *x, SensProfPartial *part, samsim_pair_stat *out,
+                                                       hipStream_t stream) {
+  const int grid = pass_grid(p, DEV_SENS_GRID, DEV_PROF_BINS);
+  if (!grid) return hipErrorInvalidValue;
+  if (p.axis == SAMSIM_PROFILE_BY_LAYER)
+    hipLaunchKernelGGL(sens_layer_kernel, dim3(grid), dim3(64), 0, stream, p.lay, x, p.n_active, p.status, p.labels, p.group, p.ncol, p.N,
+                       p.origin, p.array, p.b0, p.nb, part);
   else
-    hipLaunchKernelGGL(sens_depth_kernel, dim3(grid), dim3(64), 0, stream, lay, x, n_active, status, labels, group, ncol, N, origin, array, b0,
-                       nb, origin == SAMSIM_PROFILE_FROM_TOP ? b0 > 0 : b0 + nb < nbins, z0, dz, part);
+    hipLaunchKernelGGL(sens_depth_kernel, dim3(grid), dim3(64), 0, stream, p.lay, x, p.n_active, p.status, p.labels, p.group, p.ncol, p.N,
+                       p.origin, p.array, p.b0, p.nb, p.lead, p.z0, p.dz, part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sens_profile_merge_kernel, dim3(1), dim3(64), 0, stream, part, grid, nb, out);
+  hipLaunchKernelGGL(sens_profile_merge_kernel, dim3(1), dim3(64), 0, stream, part, grid, p.nb, out);
   return hipGetLastError();
 }

@@ -5,7 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "samsim_device.h"
+#include "samsim_profile.h"
 
 // One pass serves one array and at most DEV_PROF_BINS bins with the grid of samsim_launch_profile -- at most DEV_PROF_GRID one-wave
 // workgroups, fixed by ncol alone --, as a pass of the profile statistics does; a wave's partial per bin is the statistics'
@@ -22,12 +22,9 @@ static_assert(DEV_WPROF_BYTES <= SAMSIM_WPROFILE_SCRATCH_BYTES, "weighted profil
 #define DEV_WPROF_LDS (sizeof(double) * DEV_PROF_BINS * (DEV_PROF_BINS + 1) + 512 + 512)
 static_assert(4 * DEV_WPROF_LDS <= (160u << 10), "four workgroups per CU, as the statistics kernels get");
 
-// samsim_wprofile.hip.  One pass: array `array`, bins [b0, b0 + nb) of the request's nbins, nb <= DEV_PROF_BINS, results to
-// out[0 .. nb).  w: the [ncol] weight row; a column counts if its status is 0, its label passes (labels null: every label does;
-// else only `group`) and w > 0.  part and out lie in the handle's scratch; the call only enqueues.
-extern "C" hipError_t samsim_launch_weighted_profile(const double *lay, const double *w, const int32_t *n_active, const int32_t *status,
-                                                     const int32_t *labels, int group, long long ncol, int N, int axis, int origin,
-                                                     int array, int b0, int nb, int nbins, double z0, double dz, WProfPartial *part,
-                                                     samsim_wstat *out, hipStream_t stream);
+// samsim_wprofile.hip.  One pass (samsim_profile.h), results to out[0 .. nb).  w: the [ncol] weight row; a column counts if its
+// status is 0, its label passes and w > 0.  part and out lie in the handle's scratch; the call only enqueues.
+extern "C" hipError_t samsim_launch_weighted_profile(ProfPass p, const double *w, WProfPartial *part, samsim_wstat *out,
+                                                     hipStream_t stream);
 
 #endif

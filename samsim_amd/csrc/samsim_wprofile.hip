@@ -1,9 +1,8 @@
 // samsim_wprofile.hip -- device-side weighted statistics of the layer profiles (samsim_get_weighted_profile_stats, include/samsim.h):
 // the posterior mean, variance, extremes and effective sample size of every depth bin, with the weight row of samsim_set_weights.
 //
-// The walk is that of the profile statistics (samsim_profile_walk.h), unchanged: one wave owns one 64-column block at a time
-// (lane = column), strides over the blocks with the grid of samsim_launch_profile and drops every finished bin value into the LDS
-// tile [bin][lane].  A column whose weight is not positive enters the walk with no active layers, as a stopped one does.  The
+// A pass is that of the profile statistics (samsim_profile.h), with their grid and their walk (samsim_profile_walk.h), which drops
+// every finished bin value into the LDS tile [bin][lane].  A column whose weight is not positive enters the walk with no active layers, as a stopped one does.  The
 // block's 64 weights lie beside the tile, as the predictor of the regressions does (samsim_sens.hip), and lane j folds row j with
 // fold_tile_weighted below: the fold of samsim_profile_fold.h with every term multiplied by its weight and the total weight W in the
 // place of the count.  At the end every wave stores its 64 partials; wprofile_merge_kernel combines them in wave order, as
@@ -84,11 +83,10 @@ __device__ __forceinline__ void fold_tile_weighted(const double *tile, const dou
 }
 
 // the lane's column of block blk: its weight (0.0 beyond ncol) and its number of active layers, 0 for a column that does not count
-__device__ __forceinline__ int counting_layers(const double *w, const int32_t *n_active, const int32_t *status, const int32_t *labels, int group,
-                                               long long ncol, long long blk, int lane, int N, double &wv) {
+__device__ __forceinline__ int counting_layers(const ProfPass &p, const double *w, long long blk, int lane, double &wv) {
   const long long col = blk * 64 + lane;
-  wv = col < ncol ? w[col] : 0.0;
-  const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
+  wv = col < p.ncol ? w[col] : 0.0;
+  const int na = active_layers(p, blk, lane);
   return wv > 0.0 ? na : 0;
 }
 
@@ -98,45 +96,19 @@ __device__ __forceinline__ void store_partials(WProfPartial *part, int lane, con
   part[(size_t)blockIdx.x * DEV_PROF_BINS + lane] = p;
 }
 
-// ---- layer axis (profile_walk::layer_block): bins [b0, b0+nb)
-__global__ void __launch_bounds__(64) wprofile_layer_kernel(const double *__restrict__ lay, const double *__restrict__ w,
-                                                            const int32_t *__restrict__ n_active, const int32_t *__restrict__ status,
-                                                            const int32_t *__restrict__ labels, int group, long long ncol, int N, int origin,
-                                                            int array, int b0, int nb, WProfPartial *__restrict__ part) {
+template <int AXIS>
+__global__ void __launch_bounds__(64) wprofile_kernel(ProfPass p, const double *__restrict__ w, WProfPartial *__restrict__ part) {
   __shared__ double tile[DEV_PROF_BINS * kTileStride];
   __shared__ unsigned long long smask[64];
   __shared__ double ws[64];   // the block's weights, lane by lane
   const int lane = threadIdx.x;
-  const long long nblk = (ncol + 63) / 64;
+  const long long nblk = (p.ncol + 63) / 64;
   WRun run{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     double wv;
-    const int na = counting_layers(w, n_active, status, labels, group, ncol, blk, lane, N, wv);
+    const int na = counting_layers(p, w, blk, lane, wv);
     TileSink sink{tile, lane, 0};
-    layer_block(lay, ncol, N, blk, lane, na, origin, array, b0, nb, sink);
-    ws[lane] = wv;
-    fold_tile_weighted(tile, ws, smask, sink.mask, lane, run);
-  }
-  store_partials(part, lane, run);
-}
-
-// ---- depth axis (profile_walk::depth_block): bins [b0, b0+nb)
-__global__ void __launch_bounds__(64) wprofile_depth_kernel(const double *__restrict__ lay, const double *__restrict__ w,
-                                                            const int32_t *__restrict__ n_active, const int32_t *__restrict__ status,
-                                                            const int32_t *__restrict__ labels, int group, long long ncol, int N, int origin,
-                                                            int array, int b0, int nb, int lead, double z0, double dz,
-                                                            WProfPartial *__restrict__ part) {
-  __shared__ double tile[DEV_PROF_BINS * kTileStride];
-  __shared__ unsigned long long smask[64];
-  __shared__ double ws[64];
-  const int lane = threadIdx.x;
-  const long long nblk = (ncol + 63) / 64;
-  WRun run{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    double wv;
-    const int na = counting_layers(w, n_active, status, labels, group, ncol, blk, lane, N, wv);
-    TileSink sink{tile, lane, 0};
-    depth_block(lay, ncol, N, blk, lane, na, origin, array, b0, nb, lead, z0, dz, sink);
+    walk_block<AXIS>(p, blk, lane, na, sink);
     ws[lane] = wv;
     fold_tile_weighted(tile, ws, smask, sink.mask, lane, run);
   }
@@ -165,21 +137,8 @@ __global__ void __launch_bounds__(64) wprofile_merge_kernel(const WProfPartial *
 
 }  // namespace
 
-extern "C" hipError_t samsim_launch_weighted_profile(const double *lay, const double *w, const int32_t *n_active, const int32_t *status,
-                                                     const int32_t *labels, int group, long long ncol, int N, int axis, int origin,
-                                                     int array, int b0, int nb, int nbins, double z0, double dz, WProfPartial *part,
-                                                     samsim_wstat *out, hipStream_t stream) {
-  const long long nblk = (ncol + 63) / 64;
-  const int grid = (int)(nblk < DEV_PROF_GRID ? nblk : DEV_PROF_GRID);
-  if (nb < 1 || nb > DEV_PROF_BINS) return hipErrorInvalidValue;
-  if (axis == SAMSIM_PROFILE_BY_LAYER)
-    hipLaunchKernelGGL(wprofile_layer_kernel, dim3(grid), dim3(64), 0, stream, lay, w, n_active, status, labels, group, ncol, N, origin,
-                       array, b0, nb, part);
-  else
-    hipLaunchKernelGGL(wprofile_depth_kernel, dim3(grid), dim3(64), 0, stream, lay, w, n_active, status, labels, group, ncol, N, origin,
-                       array, b0, nb, origin == SAMSIM_PROFILE_FROM_TOP ? b0 > 0 : b0 + nb < nbins, z0, dz, part);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(wprofile_merge_kernel, dim3(1), dim3(64), 0, stream, part, grid, nb, out);
-  return hipGetLastError();
+extern "C" hipError_t samsim_launch_weighted_profile(ProfPass p, const double *w, WProfPartial *part, samsim_wstat *out,
+                                                     hipStream_t stream) {
+  return launch_tile_pass(wprofile_kernel<SAMSIM_PROFILE_BY_LAYER>, wprofile_kernel<SAMSIM_PROFILE_BY_DEPTH>, wprofile_merge_kernel,
+                          DEV_PROF_GRID, p, stream, part, out, w);
 }

@@ -382,3 +382,64 @@ def test_row_plan_places_every_item_by_first_fit(tmp_path):
                            "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
+
+
+PASS_PLAN_PROGRAM = r'''
+#include <cstdio>
+#include <cstdlib>
+#include "samsim_pass_plan.h"
+
+#define CHECK(c) do { if (!(c)) { std::printf("line %d: %s (nbins %d, chunk %d, origin %d, narrays %d, pass %d)\n", __LINE__, #c, g_nbins, g_chunk, g_origin, g_narrays, g_pass); std::exit(1); } } while (0)
+static int g_nbins, g_chunk, g_origin, g_narrays, g_pass;
+
+int main() {
+  const int NBINS[7] = {1, 63, 64, 65, 128, 129, 1024};
+  const int chunks[3] = {dev_hist_chunk(40), dev_hist_chunk(254), dev_hist_chunk(1022)};   // the launcher's own rule
+  CHECK(chunks[0] == 64 && chunks[1] == 42 && chunks[2] == 14);   // 64 and the two smaller chunks
+  const int origins[2] = {SAMSIM_PROFILE_FROM_TOP, SAMSIM_PROFILE_FROM_BOTTOM};
+  int passes = 0;
+  for (int in = 0; in < 7; ++in)
+    for (int ic = 0; ic < 3; ++ic)
+      for (int io = 0; io < 2; ++io)
+        for (int ia = 0; ia < 2; ++ia) {
+          g_nbins = NBINS[in]; g_chunk = chunks[ic]; g_origin = origins[io]; g_narrays = ia ? 8 : 1;
+          g_pass = 0;
+          int array = 0, next = 0;   // the array being tiled and the bin its next pass must begin at
+          const int rc = pass_plan(g_narrays, g_nbins, g_chunk, g_origin, [&](const PassSpan &s) {
+            if (next == g_nbins) { ++array; next = 0; }   // the previous array is complete: the next one begins
+            CHECK(s.array == array && array < g_narrays);
+            CHECK(s.b0 == next && s.nb >= 1 && s.nb <= g_chunk && s.b0 + s.nb <= g_nbins);
+            const bool first = s.b0 == 0, last = s.b0 + s.nb == g_nbins;
+            CHECK(s.lead == (g_origin == SAMSIM_PROFILE_FROM_TOP ? !first : !last));
+            next = s.b0 + s.nb;
+            ++g_pass;
+            return 0;
+          });
+          CHECK(rc == 0 && array == g_narrays - 1 && next == g_nbins);   // every array tiled to its end, none left out
+          CHECK(g_pass == g_narrays * ((g_nbins + g_chunk - 1) / g_chunk));
+          passes += g_pass;
+        }
+  // the first value that is not 0 ends the enumeration and comes back
+  g_pass = 0;
+  CHECK(pass_plan(8, 129, 64, SAMSIM_PROFILE_FROM_TOP, [&](const PassSpan &) { return ++g_pass == 4 ? -3 : 0; }) == -3 && g_pass == 4);
+  std::printf("ok %d passes\n", passes);
+  return 0;
+}
+'''
+
+
+def test_pass_plan_tiles_every_array_once_and_marks_the_leading_passes(tmp_path):
+    """samsim_pass_plan.h compiled alone by g++: nbins in {1, 63, 64, 65, 128, 129, 1024} x chunk in {64, 42, 14} (what a pass of the
+    statistics serves and what dev_hist_chunk gives at 40, 254 and 1022 value bins) x both origins x 1 and 8 arrays.  The passes
+    tile [0, nbins) exactly once per array, the arrays in order and b0 ascending, every nb <= chunk, and lead is set exactly for the
+    passes that do not begin where the walk begins: from the top every pass but the first, from the bottom every pass but the last."""
+    import os
+    import subprocess
+    from tests.helpers import ROOT
+    src = tmp_path / "pass_plan.cpp"
+    src.write_text(PASS_PLAN_PROGRAM)
+    exe = tmp_path / "pass_plan"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "samsim_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Do two builds of the library return the same bytes from the profile statistics?  Writes profile_stats_raw (T, S_bu, psi_l, thick)
-of eight requests -- both axes, both origins, one and two passes, two of them grouped -- on the day-345 melt ensemble tiled over
-70 001 columns (200 steps, three stopped columns, labels = column mod 9) for the library selected by SAMSIM_HIP_LIB; run it once
-per build, a process each, and compare the files with --compare.
+"""Do two builds of the library return the same bytes from the four reductions of the layer profiles?  Writes, for eight requests
+-- both axes, both origins, one and two passes, two of them grouped -- on the day-345 melt ensemble tiled over 70 001 columns (200
+steps, three stopped columns, labels = column mod 9): the profile statistics, the regressions on dT2m and the weighted statistics
+(Gauss weight on the ice thickness) of T, S_bu, psi_l and thick, and the joint histograms of T at 40 and at 254 value bins (one
+and two passes at 64 depth bins or fewer, two and three at 100) for the library selected by SAMSIM_HIP_LIB; run it once per
+build, a process each, and compare the files with --compare.
 
     SAMSIM_HIP_LIB=.../libsamsim_hip_parent.so python tools/profile_stats_bytes.py --out out/parent.npz
     python tools/profile_stats_bytes.py --out out/new.npz
@@ -25,6 +27,29 @@ REQUESTS = [dict(axis="layer", origin="top"), dict(axis="layer", origin="bottom"
             dict(axis="depth", origin="top", nbins=100, dz=0.02), dict(axis="depth", origin="bottom", nbins=100, dz=0.02),
             dict(axis="depth", origin="top", nbins=100, dz=0.02, group=4), dict(axis="layer", origin="bottom", group=7)]
 NAMES = ["T", "S_bu", "psi_l", "thick"]
+# family -> what it calls; every family serves every request on the same handle
+FAMILIES = {"profile_stats": "samsim_get_profile_stats / samsim_get_group_profile_stats",
+            "profile_regression": "samsim_get_profile_regression, predictor dT2m",
+            "weighted_profile_stats": "samsim_get_weighted_profile_stats after samsim_set_weights(GAUSS on thickness, scale 0.1)",
+            "profile_histogram_40": "samsim_get_profile_histogram of T, 40 value bins of 0.5 from -20",
+            "profile_histogram_254": "samsim_get_profile_histogram of T, 254 value bins of 0.08 from -20"}
+
+
+def results(g, family, rq):
+    """the bytes one family returns for one request"""
+    if family == "profile_stats":
+        q = g.profile_stats(NAMES, **rq)
+    elif family == "profile_regression":
+        q = g.profile_regression(NAMES, "dT2m", **rq)
+    elif family == "weighted_profile_stats":
+        q = g.weighted_profile_stats(NAMES, **rq)
+    else:
+        nv, dv = (40, 0.5) if family == "profile_histogram_40" else (254, 0.08)
+        h = g.profile_histogram("T", nv, -20.0, dv, **rq)
+        assert int(h.sum()) > 0
+        return h.tobytes()
+    assert max(int(q[n]["count"].max()) for n in NAMES) > 0
+    return b"".join(q[n].tobytes() for n in NAMES)
 
 
 def main():
@@ -34,17 +59,19 @@ def main():
     a = ap.parse_args()
     if a.compare:
         x, y = np.load(a.compare[0]), np.load(a.compare[1])
-        out = {"what": "samsim_get_profile_stats / samsim_get_group_profile_stats (profile_stats_raw: T, S_bu, psi_l, thick) of two builds "
-                       "of the library, a process per library; day-345 melt ensemble tiled over 70 001 columns, 200 steps, three stopped "
-                       "columns, labels = column mod 9 for the grouped requests; sha256 over the bytes of the four arrays' results per request",
-               "parent_lib_md5": str(x["lib_md5"]), "new_lib_md5": str(y["lib_md5"]), "requests": []}
+        out = {"what": "the four reductions of the layer profiles (T, S_bu, psi_l, thick; the histograms T) of two builds of the library, "
+                       "a process per library, every request on the same handle; day-345 melt ensemble tiled over 70 001 columns, 200 "
+                       "steps, three stopped columns, labels = column mod 9 for the grouped requests; sha256 over the bytes of a "
+                       "family's results per request",
+               "families": FAMILIES, "parent_lib_md5": str(x["lib_md5"]), "new_lib_md5": str(y["lib_md5"]), "requests": []}
         total, same_all = 0, True
         for i, rq in enumerate(REQUESTS):
-            u, v = x[f"r{i}"].tobytes(), y[f"r{i}"].tobytes()
-            total += len(u)
-            same_all = same_all and u == v
-            out["requests"].append({"request": rq, "parent_sha256": hashlib.sha256(u).hexdigest(), "new_sha256": hashlib.sha256(v).hexdigest(),
-                                    "same_bytes": u == v})
+            for fam in FAMILIES:
+                u, v = x[f"{fam}{i}"].tobytes(), y[f"{fam}{i}"].tobytes()
+                total += len(u)
+                same_all = same_all and u == v
+                out["requests"].append({"family": fam, "request": rq, "parent_sha256": hashlib.sha256(u).hexdigest(),
+                                        "new_sha256": hashlib.sha256(v).hexdigest(), "same_bytes": u == v})
         out["bytes_compared"], out["all_bytes_identical"] = total, bool(same_all)
         print(json.dumps(out, indent=1))
         sys.exit(0 if same_all else 1)
@@ -65,13 +92,13 @@ def main():
     g.step(200)
     assert (g.get_status()[0] != 0).sum() == 3
     g.set_groups((np.arange(ncol) % 9).astype(np.int32), ngroups=9)
+    assert g.set_weights("thickness", "gauss", 0.1)["n_pos"] > 0
     res = {"lib_md5": bench.lib_md5()}
     for i, rq in enumerate(REQUESTS):
-        q = g.profile_stats(NAMES, **rq)
-        assert max(int(q[n]["count"].max()) for n in NAMES) > 0
-        res[f"r{i}"] = np.frombuffer(b"".join(q[n].tobytes() for n in NAMES), dtype=np.uint8)
+        for fam in FAMILIES:
+            res[f"{fam}{i}"] = np.frombuffer(results(g, fam, rq), dtype=np.uint8)
     np.savez(a.out, **res)
-    print(json.dumps({"lib_md5": res["lib_md5"], "out": a.out, "bytes": int(sum(res[f"r{i}"].size for i in range(len(REQUESTS))))}))
+    print(json.dumps({"lib_md5": res["lib_md5"], "out": a.out, "bytes": int(sum(v.size for k, v in res.items() if k != "lib_md5"))}))
 
 
 if __name__ == "__main__":
