@@ -532,6 +532,24 @@ int func_refresh_for(samsim_handle *h, int32_t nslots, const int32_t *slots) {
 bool good_group(const samsim_handle *h, int32_t group) { return group == -1 || (group >= 0 && h->groups && group < h->ngroups); }
 // the label row a reduction over `group` reads: none where every column counts
 const int32_t *labels_for(const samsim_handle *h, int32_t group) { return group >= 0 ? h->groups : nullptr; }
+// the columns a slot reduction over `group` ranges over (samsim_slot_walk.h)
+slot_walk::ColSet col_set(const samsim_handle *h, int32_t group) {
+  return slot_walk::ColSet{{h->n_active, h->status, labels_for(h, group)}, group, h->ncol};
+}
+// the columns a per-label reduction ranges over: every group of samsim_set_groups at once, or without labels one group of all
+slot_walk::LabelSet label_set(const samsim_handle *h, bool by_group) {
+  return slot_walk::LabelSet{{h->n_active, h->status, by_group ? h->groups : nullptr}, h->ncol};
+}
+// count, mean[nslots] and cov[nslots][nslots] of a covariance result (CovResult, WCovResult), copied from the device to the caller
+template <class R>
+int fetch_cov(samsim_handle *h, const R *d_out, int32_t nslots, R *res, int64_t *count, double *mean, double *cov) {
+  HIPCHK(hipMemcpyAsync(res, d_out, sizeof(R), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *count = res->count;
+  std::memcpy(mean, res->mean, sizeof(double) * (size_t)nslots);
+  std::memcpy(cov, res->cov, sizeof(double) * (size_t)nslots * (size_t)nslots);
+  return SAMSIM_OK;
+}
 
 // a scratch buffer of the handle: allocated by the first call that needs it and kept
 hipError_t scratch(void **buf, size_t bytes) { return *buf ? hipSuccess : hipMalloc(buf, bytes); }
@@ -1191,7 +1209,7 @@ int samsim_get_group_stats(samsim_handle *h, int32_t nslots, const int32_t *slot
   // one pass per slot, all on the handle's stream: a slot's results have left the scratch before the next slot's merge writes them
   for (int i = 0; i < nslots; ++i) {
     const double *row = slot_row(h, slots[i]);
-    HIPCHK(samsim_launch_group_stats(row, h->n_active, h->status, h->groups, h->ncol, h->ngroups, d_part, d_out, h->stream));
+    HIPCHK(samsim_launch_group_stats(label_set(h, true), row, h->ngroups, d_part, d_out, h->stream));
     HIPCHK(hipMemcpyAsync(out + (size_t)i * ng, d_out, sizeof(samsim_stat) * ng, hipMemcpyDeviceToHost, h->stream));
   }
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1233,8 +1251,7 @@ int samsim_get_histogram(samsim_handle *h, int32_t slot, const samsim_hist_bins 
   const size_t bytes = sizeof(int64_t) * (size_t)ng * (size_t)(e.nvbins + 2);
   const double *row = slot_row(h, slot);
   HIPCHK(hipMemsetAsync(h->d_hist, 0, bytes, h->stream));
-  HIPCHK(samsim_launch_hist(row, h->n_active, h->status, by_group ? h->groups : nullptr, h->ncol, ng, e,
-                            (unsigned long long *)h->d_hist, h->stream));
+  HIPCHK(samsim_launch_hist(label_set(h, by_group != 0), row, ng, e, (unsigned long long *)h->d_hist, h->stream));
   HIPCHK(hipMemcpyAsync(counts, h->d_hist, bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
@@ -1275,15 +1292,9 @@ int samsim_get_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots
   HIPCHK(scratch(&h->d_sens, kSensScratch));
   double *d_part = (double *)h->d_sens;
   CovResult *d_out = (CovResult *)((char *)h->d_sens + DEV_SENS_PART_BYTES);
-  HIPCHK(samsim_launch_covariance(rows, nslots, h->n_active, h->status, labels_for(h, group), group, h->ncol, d_part, d_out,
-                                  h->stream));
+  HIPCHK(samsim_launch_covariance(col_set(h, group), rows, nslots, d_part, d_out, h->stream));
   CovResult res;
-  HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(CovResult), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  *count = res.count;
-  std::memcpy(mean, res.mean, sizeof(double) * (size_t)nslots);
-  std::memcpy(cov, res.cov, sizeof(double) * (size_t)nslots * (size_t)nslots);
-  return SAMSIM_OK;
+  return fetch_cov(h, d_out, nslots, &res, count, mean, cov);
 }
 
 int samsim_get_profile_regression(samsim_handle *h, const samsim_profile_request *rq, int32_t predictor_slot, int32_t group,
@@ -1768,8 +1779,7 @@ int samsim_set_weights(samsim_handle *h, const samsim_weight_spec *spec, samsim_
   WeightPartial *d_part = (WeightPartial *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
   WeightPartial *d_out = (WeightPartial *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
   const double c = spec->kind == SAMSIM_WEIGHT_GAUSS ? 0.5 / spec->scale : 0.0;
-  HIPCHK(samsim_launch_set_weights(slot_row(h, spec->slot), h->n_active, h->status, labels_for(h, spec->group), spec->group,
-                                   h->ncol, spec->kind, c, row, d_part, d_out, h->stream));
+  HIPCHK(samsim_launch_set_weights(col_set(h, spec->group), slot_row(h, spec->slot), spec->kind, c, row, d_part, d_out, h->stream));
   WeightPartial res;
   HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(WeightPartial), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1799,8 +1809,7 @@ int samsim_get_weighted_stats(samsim_handle *h, int32_t nslots, const int32_t *s
   HIPCHK(scratch(&h->d_weight, kWeightScratch));
   WStatPartial *d_part = (WStatPartial *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
   samsim_wstat *d_out = (samsim_wstat *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
-  HIPCHK(samsim_launch_weighted_stats(rows, nslots, h->weight_row, h->n_active, h->status, labels_for(h, group), group, h->ncol,
-                                      d_part, d_out, h->stream));
+  HIPCHK(samsim_launch_weighted_stats(col_set(h, group), rows, nslots, h->weight_row, d_part, d_out, h->stream));
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_wstat) * (size_t)nslots, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
@@ -1822,8 +1831,7 @@ int samsim_get_weighted_histogram(samsim_handle *h, int32_t slot, const samsim_h
   HIPCHK(scratch(&h->d_weight, kWeightScratch));
   double *d_tables = (double *)((char *)h->d_weight + DEV_WEIGHT_TABLES_AT);
   double *d_out = (double *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
-  HIPCHK(samsim_launch_weighted_hist(slot_row(h, slot), h->weight_row, h->n_active, h->status, labels_for(h, group), group,
-                                     h->ncol, e, d_tables, d_out, h->stream));
+  HIPCHK(samsim_launch_weighted_hist(col_set(h, group), slot_row(h, slot), h->weight_row, e, d_tables, d_out, h->stream));
   HIPCHK(hipMemcpyAsync(wsum, d_out, sizeof(double) * (size_t)(e.nvbins + 2), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
@@ -1855,21 +1863,17 @@ int samsim_get_weighted_covariance(samsim_handle *h, int32_t nslots, const int32
   // every check first: nothing below touches the device before the request is known to be good
   if (!h || !slots || !count || !sum_w || !sum_w2 || !mean || !cov) return SAMSIM_ERR_ARG;
   SensRows rows{};
-  const int rc = slot_rows(h, nslots, slots, true, group, &rows);
+  int rc = slot_rows(h, nslots, slots, true, group, &rows);
   if (rc) return rc;
   HIPCHK(scratch(&h->d_weight, kWeightScratch));
   double *d_part = (double *)((char *)h->d_weight + DEV_WEIGHT_PART_AT);
   WCovResult *d_out = (WCovResult *)((char *)h->d_weight + DEV_WEIGHT_RESULT_AT);
-  HIPCHK(samsim_launch_weighted_covariance(rows, nslots, h->weight_row, h->n_active, h->status, labels_for(h, group), group,
-                                           h->ncol, d_part, d_out, h->stream));
+  HIPCHK(samsim_launch_weighted_covariance(col_set(h, group), rows, nslots, h->weight_row, d_part, d_out, h->stream));
   WCovResult res;
-  HIPCHK(hipMemcpyAsync(&res, d_out, sizeof(WCovResult), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  *count = res.count;
+  rc = fetch_cov(h, d_out, nslots, &res, count, mean, cov);
+  if (rc) return rc;
   *sum_w = res.sum_w;
   *sum_w2 = res.sum_w2;
-  std::memcpy(mean, res.mean, sizeof(double) * (size_t)nslots);
-  std::memcpy(cov, res.cov, sizeof(double) * (size_t)nslots * (size_t)nslots);
   return SAMSIM_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/samsim.h"
+#include "samsim_slot_walk.h"
 
 // One pass reduces one [ncol] row with a fixed grid of one-wave workgroups; every wave leaves one partial per group, merged in
 // wave order.  The grid is the largest that keeps the waves' partials within DEV_GROUP_PART_ENTRIES, at most DEV_GROUP_GRID
@@ -15,15 +16,14 @@
 struct GroupPartial { double mean, m2, mn, mx; long long n; };
 
 static inline int dev_group_waves(long long ncol, int ngroups) {
-  const long long nblk = (ncol + 63) / 64;
-  long long w = DEV_GROUP_PART_ENTRIES / ngroups;
-  w = w < DEV_GROUP_GRID ? w : DEV_GROUP_GRID;
-  return (int)(nblk < w ? nblk : w);
+  const long long w = DEV_GROUP_PART_ENTRIES / ngroups;
+  return slot_walk::slot_grid(ncol, w < DEV_GROUP_GRID ? w : DEV_GROUP_GRID);
 }
 
-// samsim_groups.hip: the statistics of one row (row, or n_active where row is null) per group, results to out[0 .. ngroups).
-// part holds dev_group_waves(ncol, ngroups) * ngroups partials and is reused by the next pass on the same stream.
-extern "C" hipError_t samsim_launch_group_stats(const double *row, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                                long long ncol, int ngroups, GroupPartial *part, samsim_stat *out, hipStream_t stream);
+// samsim_groups.hip: the statistics of one row (row, or n_active where row is null) per group of cs.labels,
+// results to out[0 .. ngroups).  part holds dev_group_waves(ncol, ngroups) * ngroups partials and is reused by the next pass on the
+// same stream.
+extern "C" hipError_t samsim_launch_group_stats(slot_walk::LabelSet cs, const double *row, int ngroups, GroupPartial *part, samsim_stat *out,
+                                                hipStream_t stream);
 
 #endif

@@ -7,6 +7,7 @@
 
 #include "samsim_pass_plan.h"
 #include "samsim_profile.h"
+#include "samsim_slot_walk.h"
 
 // A row of counts has W = nvbins + 2 entries.  Both reductions run a fixed grid of at most DEV_HIST_GRID one-wave workgroups; a
 // wave counts in 32-bit entries of an LDS table and adds what it found to the 64-bit result table in device memory with integer
@@ -46,10 +47,10 @@ __device__ __forceinline__ int hist_entry(double v, const HistEdges &e) {
 }
 
 // samsim_hist.hip.  counts: the 64-bit result table in device memory, zero before the first pass of a request.
-// Scalars: the histogram of one row (row, or n_active where row is null) per group -- labels null: one group of every column with
-// status 0 --, counts[ngroups][W].
-extern "C" hipError_t samsim_launch_hist(const double *row, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                         long long ncol, int ngroups, HistEdges e, unsigned long long *counts, hipStream_t stream);
+// Scalars: the histogram of one row (row, or n_active where row is null) per group of cs.labels -- null: one group of every column
+// with status 0 --, counts[ngroups][W].
+extern "C" hipError_t samsim_launch_hist(slot_walk::LabelSet cs, const double *row, int ngroups, HistEdges e, unsigned long long *counts,
+                                         hipStream_t stream);
 // Profiles, one pass (samsim_profile.h) with nb <= dev_hist_chunk(nvbins): rows b0 .. b0+nb-1 of counts[nbins][W].
 extern "C" hipError_t samsim_launch_profile_hist(ProfPass p, HistEdges e, unsigned long long *counts, hipStream_t stream);
 

@@ -2,11 +2,10 @@
 // include/samsim.h): of a per-column scalar over all columns or per group, and of the layer profiles as a joint histogram over
 // depth bin x value bin.
 //
-// Scalars: one wave owns one 64-column block at a time (lane = column) and strides over the blocks with a fixed grid, as
-// group_stats_kernel does; its loads of the row, of status and of the labels are coalesced and the next block's are under way while
-// this block is counted.  Profiles: a pass of samsim_profile.h, whose walk (samsim_profile_walk.h) fills the LDS tile [bin][lane];
-// then lane j walks row j of the tile and increments its own row of the count table -- no atomics in the loop.  Either way a wave
-// counts in 32-bit LDS entries and adds its table to the 64-bit result with integer atomics at the end (samsim_hist.h); there is no
+// Scalars: the walk of samsim_slot_walk.h, every column counted where its label and its value say.
+// Profiles: a pass of samsim_profile.h, whose walk (samsim_profile_walk.h) fills the LDS tile [bin][lane]; then lane j walks
+// row j of the tile and increments its own row of the count table -- no atomics in the loop.  Either way a wave counts in
+// 32-bit LDS entries and adds its table to the 64-bit result with integer atomics at the end (samsim_hist.h); there is no
 // floating-point atomic and no floating-point sum at all, so two calls return the same bytes.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +15,7 @@
 namespace {
 
 using namespace profile_walk;
+using namespace slot_walk;
 
 // what a wave counted, added to the 64-bit result
 __device__ __forceinline__ void flush_table(const uint32_t *table, int n, int lane, unsigned long long *out) {
@@ -25,43 +25,25 @@ __device__ __forceinline__ void flush_table(const uint32_t *table, int n, int la
   }
 }
 
-// the lane's column of block blk: its group (-1: stopped, unlabelled or beyond ncol; without labels 0) and its value
-__device__ __forceinline__ void load_column(const double *row, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                            long long ncol, int ngroups, long long blk, int lane, int &lab, double &v) {
-  const long long col = blk * 64 + lane;
-  lab = -1; v = 0.0;
-  if (col < ncol) {
-    const int l = labels ? labels[col] : 0;
-    lab = (status[col] == 0 && l < ngroups) ? l : -1;
-    v = row ? row[col] : (double)n_active[col];
-  }
-}
-
 // LDS: the wave's table [ngroups][W] of 32-bit counts in LDS (dev_hist_in_lds); else every lane adds into the result itself
 template <bool LDS>
-__global__ void __launch_bounds__(64) hist_kernel(const double *__restrict__ row, const int32_t *__restrict__ n_active,
-                                                  const int32_t *__restrict__ status, const int32_t *__restrict__ labels, long long ncol,
-                                                  int ngroups, HistEdges e, unsigned long long *__restrict__ counts) {
+__global__ void __launch_bounds__(64) hist_kernel(const double *__restrict__ row, LabelSet cs, int ngroups, HistEdges e,
+                                                  unsigned long long *__restrict__ counts) {
   extern __shared__ uint32_t table[];   // [ngroups][W]
   const int lane = threadIdx.x, W = e.nvbins + 2;
   if (LDS) {
     for (int i = lane; i < ngroups * W; i += 64) table[i] = 0;
     __syncthreads();
   }
-  const long long nblk = (ncol + 63) / 64;
-  int lab, lab_next = -1;
-  double v, v_next = 0.0;
-  load_column(row, n_active, status, labels, ncol, ngroups, blockIdx.x, lane, lab, v);
-  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    // the next block's loads are under way while this block is counted
-    if (blk + gridDim.x < nblk) load_column(row, n_active, status, labels, ncol, ngroups, blk + gridDim.x, lane, lab_next, v_next);
-    if (lab >= 0) {
-      const int i = lab * W + hist_entry(v, e);
-      if (LDS) atomicAdd(table + i, 1u);
-      else atomicAdd(counts + i, 1ull);
-    }
-    lab = lab_next; v = v_next;
-  }
+  walk_blocks<LabelCol>(
+      cs.ncol, lane, [&](long long blk, int ln, LabelCol &c) { load_label_col(cs, row, ngroups, blk, ln, c); },
+      [&](long long, const LabelCol &c) {
+        if (c.lab >= 0) {
+          const int i = c.lab * W + hist_entry(c.v, e);
+          if (LDS) atomicAdd(table + i, 1u);
+          else atomicAdd(counts + i, 1ull);
+        }
+      });
   if (LDS) {
     __syncthreads();
     flush_table(table, ngroups * W, lane, counts);
@@ -111,7 +93,7 @@ __global__ void __launch_bounds__(64) hist_layer_kernel(const double *__restrict
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x, stride = (e.nvbins + 2) | 1;
   const ProfLds p = carve(lds, chunk, stride, lane);
-  const long long nblk = (ncol + 63) / 64;
+  const long long nblk = col_blocks(ncol);
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
     TileSink sink{p.tile, lane, 0};
@@ -128,7 +110,7 @@ __global__ void __launch_bounds__(64) hist_depth_kernel(const double *__restrict
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x, stride = (e.nvbins + 2) | 1;
   const ProfLds p = carve(lds, chunk, stride, lane);
-  const long long nblk = (ncol + 63) / 64;
+  const long long nblk = col_blocks(ncol);
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int na = active_layers(n_active, status, labels, group, ncol, blk, lane, N);
     TileSink sink{p.tile, lane, 0};
@@ -140,15 +122,14 @@ __global__ void __launch_bounds__(64) hist_depth_kernel(const double *__restrict
 
 }  // namespace
 
-extern "C" hipError_t samsim_launch_hist(const double *row, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                         long long ncol, int ngroups, HistEdges e, unsigned long long *counts, hipStream_t stream) {
-  const long long nblk = (ncol + 63) / 64;
-  const int grid = (int)(nblk < DEV_HIST_GRID ? nblk : DEV_HIST_GRID);
+extern "C" hipError_t samsim_launch_hist(LabelSet cs, const double *row, int ngroups, HistEdges e, unsigned long long *counts,
+                                         hipStream_t stream) {
+  const int grid = slot_grid(cs.ncol, DEV_HIST_GRID);
   if (dev_hist_in_lds(ngroups, e.nvbins))
-    hipLaunchKernelGGL(hist_kernel<true>, dim3(grid), dim3(64), sizeof(uint32_t) * (size_t)ngroups * (e.nvbins + 2), stream, row, n_active,
-                       status, labels, ncol, ngroups, e, counts);
+    hipLaunchKernelGGL(hist_kernel<true>, dim3(grid), dim3(64), sizeof(uint32_t) * (size_t)ngroups * (e.nvbins + 2), stream, row, cs,
+                       ngroups, e, counts);
   else
-    hipLaunchKernelGGL(hist_kernel<false>, dim3(grid), dim3(64), 0, stream, row, n_active, status, labels, ncol, ngroups, e, counts);
+    hipLaunchKernelGGL(hist_kernel<false>, dim3(grid), dim3(64), 0, stream, row, cs, ngroups, e, counts);
   return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "samsim_profile.h"
+#include "samsim_slot_walk.h"
 
 // Both reductions run a fixed grid of at most DEV_SENS_GRID one-wave workgroups (a wave per 64-column block at a time), fixed by
 // ncol alone; every wave leaves one partial, merged in wave order.
@@ -40,10 +41,9 @@ static_assert(sizeof(CovResult) <= DEV_SENS_RESULT_BYTES, "the covariance result
 #define DEV_SENS_PROFILE_LDS (sizeof(double) * DEV_PROF_BINS * (DEV_PROF_BINS + 1) + 512 + 512)
 static_assert(4 * DEV_SENS_PROFILE_LDS <= (160u << 10), "four regression workgroups per CU, as the statistics kernels get");
 
-// samsim_sens.hip.  labels: null (every column with status 0 counts), or the label row of samsim_set_groups, of which only the
-// columns with label `group` count.  part and out lie in the handle's scratch; the calls only enqueue.
-extern "C" hipError_t samsim_launch_covariance(SensRows rows, int nslots, const int32_t *n_active, const int32_t *status,
-                                               const int32_t *labels, int group, long long ncol, double *part, CovResult *out,
+// samsim_sens.hip.  cs: the columns that count (samsim_slot_walk.h).  part and out lie in the handle's scratch; the calls only
+// enqueue.
+extern "C" hipError_t samsim_launch_covariance(slot_walk::ColSet cs, SensRows rows, int nslots, double *part, CovResult *out,
                                                hipStream_t stream);
 // one pass (samsim_profile.h), results to out[0 .. nb); x: the predictor's [ncol] row, or null for n_active
 extern "C" hipError_t samsim_launch_profile_regression(ProfPass p, const double *x, SensProfPartial *part, samsim_pair_stat *out,

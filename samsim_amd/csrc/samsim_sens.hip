@@ -2,12 +2,8 @@
 // joint second moments of the per-column scalars, and per depth bin the joint moments of a layer profile and one per-column
 // predictor.
 //
-// Scalars: one wave owns one 64-column block at a time (lane = column) and strides over the blocks with a fixed grid, as
-// group_stats_kernel and hist_kernel do; the nslots row loads, status and the labels are coalesced and the next block's are under
-// way while this block is consumed.  Every lane keeps its own running n, nslots means and nslots (nslots + 1) / 2 co-moments in
-// registers (a template on nslots: every index is a compile-time one) and applies Welford's update to them.  At the end the 64
-// lanes are combined in lane order through LDS (Chan's pairwise update), one thread per pair of slots, and the wave's partial is
-// stored; cov_merge_kernel combines the waves' partials in wave order.
+// Scalars: the walk and the bracket of samsim_slot_walk.h.  Every lane applies Welford's update to its own running moments of the
+// nslots rows (a template on nslots); the lanes and then the waves are combined with Chan's pairwise update.
 //
 // Profiles: a pass of samsim_profile.h, whose walk (samsim_profile_walk.h) fills the LDS tile [bin][lane]; the block's 64
 // predictor values lie beside it, and lane j folds row j with the statistics' own fold and merge (samsim_profile_fold.h) with the
@@ -24,10 +20,9 @@ namespace {
 
 using namespace profile_walk;
 using namespace profile_fold;
+using namespace slot_walk;
 
 // ---------------------------------------------------------------------------------------------------------------- scalars
-
-constexpr int kLaneStride = 65;   // doubles from one quantity's 64 lane values to the next in LDS
 
 // Running moments of one pair of slots (i, j): n columns, the two means, the sum of products of deviations.  Every update is
 // symmetric in i and j down to the bits (dx * dy == dy * dx), so a slot listed twice gives the bytes of its variance.
@@ -49,71 +44,44 @@ struct PairAcc {
     c = c + c_b + di * dj * w;
     n = nn;
   }
+  __device__ __forceinline__ void absorb(const PairAcc &b) {
+    if (b.n > 0) add(b.n, b.mi, b.mj, b.c);
+  }
 };
 
-// pair p of the upper triangle of ns slots, row by row: (0,0), (0,1), .. (0,ns-1), (1,1), ..
-__device__ __forceinline__ void pair_of(int p, int ns, int &i, int &j) {
-  i = 0;
-  while (p >= ns - i) { p -= ns - i; ++i; }
-  j = i + p;
-}
-
-// the lane's column of block blk: whether it counts (status 0, within ncol, the right label) and its values of the NS slots
+// Every lane keeps its own running n, NS means and NS (NS + 1) / 2 co-moments in registers (every index is a compile-time one);
+// at the end the 64 lanes in lane order through LDS, one thread per pair of slots, and the wave's partial is stored.
 template <int NS>
-__device__ __forceinline__ void load_column(const SensRows &rows, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                            int group, long long ncol, long long blk, int lane, bool &ok, double (&v)[NS]) {
-  const long long col = blk * 64 + lane;
-  ok = false;
-#pragma unroll
-  for (int i = 0; i < NS; ++i) v[i] = 0.0;
-  if (col < ncol) {
-    ok = status[col] == 0 && (!labels || labels[col] == group);
-#pragma unroll
-    for (int i = 0; i < NS; ++i) v[i] = rows.row[i] ? rows.row[i][col] : (double)n_active[col];
-  }
-}
-
-template <int NS>
-__global__ void __launch_bounds__(64) cov_kernel(SensRows rows, const int32_t *__restrict__ n_active, const int32_t *__restrict__ status,
-                                                 const int32_t *__restrict__ labels, int group, long long ncol, double *__restrict__ part) {
+__global__ void __launch_bounds__(64) cov_kernel(SensRows rows, ColSet cs, double *__restrict__ part) {
   constexpr int NP = NS * (NS + 1) / 2;
   __shared__ double s[(1 + NS + NP) * kLaneStride];   // [n, means, co-moments][lane]
   const int lane = threadIdx.x;
-  const long long nblk = (ncol + 63) / 64;
   long long n = 0;
   double mean[NS], C[NP];
 #pragma unroll
   for (int i = 0; i < NS; ++i) mean[i] = 0.0;
 #pragma unroll
   for (int p = 0; p < NP; ++p) C[p] = 0.0;
-  bool ok, ok_next = false;
-  double v[NS], v_next[NS];
-  load_column<NS>(rows, n_active, status, labels, group, ncol, blockIdx.x, lane, ok, v);
-  for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    // the next block's loads are under way while this block is consumed
-    if (blk + gridDim.x < nblk) load_column<NS>(rows, n_active, status, labels, group, ncol, blk + gridDim.x, lane, ok_next, v_next);
-    if (ok) {
-      // Welford: the first value of a lane is its mean exactly (0 + v / 1), equal values leave the means and the co-moments alone
-      // (every d is 0).  The co-moment takes d_i * d_j * (n - 1) / n, the form of the update that is symmetric in i and j.
-      n += 1;
-      const double dn = (double)n, f = (double)(n - 1) / dn;
-      double d[NS];
+  walk_blocks<Cols<NS>>(
+      cs.ncol, lane, [&](long long blk, int ln, Cols<NS> &c) { load_cols<NS>(cs, rows.row, nullptr, blk, ln, c); },
+      [&](long long, const Cols<NS> &c) {
+        if (!c.ok) return;
+        // Welford: the first value of a lane is its mean exactly (0 + v / 1), equal values leave the means and the co-moments
+        // alone (every d is 0).  The co-moment takes d_i * d_j * (n - 1) / n, the form of the update that is symmetric in i and j.
+        n += 1;
+        const double dn = (double)n, f = (double)(n - 1) / dn;
+        double d[NS];
 #pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        d[i] = v[i] - mean[i];
-        mean[i] = mean[i] + d[i] / dn;
-      }
-      int p = 0;
+        for (int i = 0; i < NS; ++i) {
+          d[i] = c.v[i] - mean[i];
+          mean[i] = mean[i] + d[i] / dn;
+        }
+        int p = 0;
 #pragma unroll
-      for (int i = 0; i < NS; ++i)
+        for (int i = 0; i < NS; ++i)
 #pragma unroll
-        for (int j = i; j < NS; ++j, ++p) C[p] = C[p] + d[i] * d[j] * f;
-    }
-    ok = ok_next;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) v[i] = v_next[i];
-  }
-  // the 64 lanes in lane order, one thread per pair of slots
+          for (int j = i; j < NS; ++j, ++p) C[p] = C[p] + d[i] * d[j] * f;
+      });
   s[lane] = (double)n;
 #pragma unroll
   for (int i = 0; i < NS; ++i) s[(1 + i) * kLaneStride + lane] = mean[i];
@@ -124,49 +92,33 @@ __global__ void __launch_bounds__(64) cov_kernel(SensRows rows, const int32_t *_
   int i, j;
   pair_of(lane, NS, i, j);
   PairAcc acc{0, 0.0, 0.0, 0.0};
-  for (int l = 0; l < 64; ++l) {
-    const long long nb = (long long)s[l];
-    if (nb > 0) acc.add(nb, s[(1 + i) * kLaneStride + l], s[(1 + j) * kLaneStride + l], s[(1 + NS + lane) * kLaneStride + l]);
-  }
+  absorb_lanes(acc, [&](int l) {
+    return PairAcc{(long long)s[l], s[(1 + i) * kLaneStride + l], s[(1 + j) * kLaneStride + l], s[(1 + NS + lane) * kLaneStride + l]};
+  });
   double *mine = part + (size_t)blockIdx.x * DEV_COV_PART;
   mine[DEV_COV_C0 + lane] = acc.c;
   if (i == j) mine[DEV_COV_MEAN0 + i] = acc.mi;
   if (lane == 0) mine[0] = (double)acc.n;
 }
 
-// One workgroup per pair of slots: lane l combines the partials of the waves [l * per, (l + 1) * per) in wave order, then lane 0
-// combines the 64 lanes' results in lane order -- the waves' partials in wave order, bracketed the same way whatever the data (as
-// group_merge_kernel does).  The pair (i, j) goes to cov[i][j] and cov[j][i]: one value, stored twice.
+// One workgroup per pair of slots: the waves' partials in wave order.  The pair (i, j) goes to cov[i][j] and cov[j][i]: one
+// value, stored twice.
 __global__ void __launch_bounds__(64) cov_merge_kernel(const double *__restrict__ part, int nwaves, int ns, CovResult *__restrict__ out) {
-  __shared__ double s_n[64], s_mi[64], s_mj[64], s_c[64];
-  const int lane = threadIdx.x, p = blockIdx.x;
+  __shared__ PairAcc s_acc[64];
+  const int p = blockIdx.x;
   int i, j;
   pair_of(p, ns, i, j);
-  const int per = (nwaves + 63) / 64;
   PairAcc acc{0, 0.0, 0.0, 0.0};
-  for (int w = lane * per; w < (lane + 1) * per && w < nwaves; ++w) {
+  const bool last = merge_waves(nwaves, acc, s_acc, threadIdx.x, [&](int w) {
     const double *q = part + (size_t)w * DEV_COV_PART;
-    const long long nb = (long long)q[0];
-    if (nb > 0) acc.add(nb, q[DEV_COV_MEAN0 + i], q[DEV_COV_MEAN0 + j], q[DEV_COV_C0 + p]);
-  }
-  s_n[lane] = (double)acc.n; s_mi[lane] = acc.mi; s_mj[lane] = acc.mj; s_c[lane] = acc.c;
-  __syncthreads();
-  if (lane != 0) return;
-  for (int l = 1; l < 64; ++l) {
-    const long long nb = (long long)s_n[l];
-    if (nb > 0) acc.add(nb, s_mi[l], s_mj[l], s_c[l]);
-  }
+    return PairAcc{(long long)q[0], q[DEV_COV_MEAN0 + i], q[DEV_COV_MEAN0 + j], q[DEV_COV_C0 + p]};
+  });
+  if (!last) return;
   const double cov = acc.n > 0 ? acc.c / (double)acc.n : 0.0;
   out->cov[i * ns + j] = cov;
   out->cov[j * ns + i] = cov;
   if (i == j) out->mean[i] = acc.n > 0 ? acc.mi : 0.0;
   if (p == 0) out->count = acc.n;
-}
-
-template <int NS>
-void launch_cov(SensRows rows, const int32_t *n_active, const int32_t *status, const int32_t *labels, int group, long long ncol, int grid,
-                double *part, hipStream_t stream) {
-  hipLaunchKernelGGL(cov_kernel<NS>, dim3(grid), dim3(64), 0, stream, rows, n_active, status, labels, group, ncol, part);
 }
 
 // --------------------------------------------------------------------------------------------------------------- profiles
@@ -195,7 +147,7 @@ __global__ void __launch_bounds__(64) sens_layer_kernel(const double *__restrict
   __shared__ unsigned long long smask[64];
   __shared__ double xs[64];   // the block's predictor values, lane by lane
   const int lane = threadIdx.x;
-  const long long nblk = (ncol + 63) / 64;
+  const long long nblk = col_blocks(ncol);
   Run run{0, 0.0, 0.0, 0.0, 0.0};
   Co co{0.0, 0.0, 0.0};
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -219,7 +171,7 @@ __global__ void __launch_bounds__(64) sens_depth_kernel(const double *__restrict
   __shared__ unsigned long long smask[64];
   __shared__ double xs[64];
   const int lane = threadIdx.x;
-  const long long nblk = (ncol + 63) / 64;
+  const long long nblk = col_blocks(ncol);
   Run run{0, 0.0, 0.0, 0.0, 0.0};
   Co co{0.0, 0.0, 0.0};
   for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
@@ -258,22 +210,12 @@ __global__ void __launch_bounds__(64) sens_profile_merge_kernel(const SensProfPa
 
 }  // namespace
 
-extern "C" hipError_t samsim_launch_covariance(SensRows rows, int nslots, const int32_t *n_active, const int32_t *status,
-                                               const int32_t *labels, int group, long long ncol, double *part, CovResult *out,
-                                               hipStream_t stream) {
-  const long long nblk = (ncol + 63) / 64;
-  const int grid = (int)(nblk < DEV_SENS_GRID ? nblk : DEV_SENS_GRID);
-  switch (nslots) {
-    case 1: launch_cov<1>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    case 2: launch_cov<2>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    case 3: launch_cov<3>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    case 4: launch_cov<4>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    case 5: launch_cov<5>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    case 6: launch_cov<6>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    case 7: launch_cov<7>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    case 8: launch_cov<8>(rows, n_active, status, labels, group, ncol, grid, part, stream); break;
-    default: return hipErrorInvalidValue;
-  }
+extern "C" hipError_t samsim_launch_covariance(ColSet cs, SensRows rows, int nslots, double *part, CovResult *out, hipStream_t stream) {
+  const int grid = slot_grid(cs.ncol, DEV_SENS_GRID);
+  const bool known = dispatch_nslots(nslots, [&](auto ns) {
+    hipLaunchKernelGGL(cov_kernel<decltype(ns)::value>, dim3(grid), dim3(64), 0, stream, rows, cs, part);
+  });
+  if (!known) return hipErrorInvalidValue;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(cov_merge_kernel, dim3(nslots * (nslots + 1) / 2), dim3(64), 0, stream, part, grid, nslots, out);

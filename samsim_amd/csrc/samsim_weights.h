@@ -49,25 +49,20 @@ struct WCovResult {
 static_assert(sizeof(double) * DEV_WCOV_PART * DEV_WEIGHT_GRID <= DEV_WEIGHT_PART_BYTES, "the covariance partials fit where the moments' do");
 static_assert(sizeof(WCovResult) <= DEV_WEIGHT_RESULT_BYTES, "the covariance result fits where a histogram row does");
 
-// samsim_weights.hip.  x: the [ncol] row of the source slot, or null for n_active.  labels: null (every column with status 0 is
-// IN), or the label row of samsim_set_groups, of which only the columns with label `group` are.  part and out lie in the handle's
-// scratch; the calls only enqueue.
+// samsim_weights.hip.  cs: the columns that are IN (samsim_slot_walk.h).  x: the [ncol] row of the source slot, or null for
+// n_active.  part and out lie in the handle's scratch; the calls only enqueue.
 // The weight row w[ncol] of `kind` (enum samsim_weight_kind) with c = 0.5 / scale; out: x_min, sum_w, sum_w2, n_in, n_pos.
-extern "C" hipError_t samsim_launch_set_weights(const double *x, const int32_t *n_active, const int32_t *status, const int32_t *labels,
-                                                int group, long long ncol, int kind, double c, double *w, WeightPartial *part,
+extern "C" hipError_t samsim_launch_set_weights(slot_walk::ColSet cs, const double *x, int kind, double c, double *w, WeightPartial *part,
                                                 WeightPartial *out, hipStream_t stream);
 // the weighted moments of the nslots rows (SensRows of samsim_sens.h: a null row is n_active) over the columns that are IN and have
 // w > 0, in one walk, to out[0 .. nslots)
-extern "C" hipError_t samsim_launch_weighted_stats(SensRows rows, int nslots, const double *w, const int32_t *n_active,
-                                                   const int32_t *status, const int32_t *labels, int group, long long ncol,
-                                                   WStatPartial *part, samsim_wstat *out, hipStream_t stream);
+extern "C" hipError_t samsim_launch_weighted_stats(slot_walk::ColSet cs, SensRows rows, int nslots, const double *w, WStatPartial *part,
+                                                   samsim_wstat *out, hipStream_t stream);
 // the sum of w per entry of the histogram of one row over the same columns: tables [grid][DEV_WEIGHT_ENTRIES], out [nvbins + 2]
-extern "C" hipError_t samsim_launch_weighted_hist(const double *x, const double *w, const int32_t *n_active, const int32_t *status,
-                                                  const int32_t *labels, int group, long long ncol, HistEdges e, double *tables, double *out,
-                                                  hipStream_t stream);
+extern "C" hipError_t samsim_launch_weighted_hist(slot_walk::ColSet cs, const double *x, const double *w, HistEdges e, double *tables,
+                                                  double *out, hipStream_t stream);
 // the weighted means and covariances of the nslots rows over the same columns, in one walk: part [grid][DEV_WCOV_PART]
-extern "C" hipError_t samsim_launch_weighted_covariance(SensRows rows, int nslots, const double *w, const int32_t *n_active,
-                                                        const int32_t *status, const int32_t *labels, int group, long long ncol,
-                                                        double *part, WCovResult *out, hipStream_t stream);
+extern "C" hipError_t samsim_launch_weighted_covariance(slot_walk::ColSet cs, SensRows rows, int nslots, const double *w, double *part,
+                                                        WCovResult *out, hipStream_t stream);
 
 #endif

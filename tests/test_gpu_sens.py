@@ -140,6 +140,20 @@ def test_a_slot_listed_twice(big):
         assert cov[i].tobytes() == cov[j].tobytes() and np.ascontiguousarray(cov[:, i]).tobytes() == np.ascontiguousarray(cov[:, j]).tobytes()
 
 
+def test_every_number_of_slots_gives_the_leading_block_of_eight(small):
+    """Every instantiation of the walk, 1 to 8 slots: the first k slots alone return count, mean[:k] and cov[:k, :k] of the call
+    with all eight, byte for byte -- a pair's chain of operations does not depend on how many slots ride along.  4 197 columns are
+    66 waves, so a lane of the merge takes two waves and the lanes 33 to 63 none, and the last block has 37 columns."""
+    g = small[0]
+    for group in (None, 1):
+        n8, mean8, cov8 = g.covariance(SLOTS, group=group)
+        assert n8 > 1000 and (np.diag(cov8)[:5] > 0.0).all()
+        for k in range(1, 9):
+            n, mean, cov = g.covariance(SLOTS[:k], group=group)
+            assert n == n8 and mean.tobytes() == mean8[:k].tobytes(), (group, k)
+            assert cov.tobytes() == np.ascontiguousarray(cov8[:k, :k]).tobytes(), (group, k)
+
+
 def test_profiles_by_layer_against_the_reference(big):
     """80 layer bins: two passes; 1 094 blocks: every wave strides"""
     g, s, status = big

@@ -473,6 +473,45 @@ def test_the_calls_are_deterministic_and_write_nothing_else(small):
     assert snapshot(g) == before
 
 
+def test_every_number_of_slots_gives_the_leading_block_of_eight(small):
+    """Every instantiation of the two walks over a list of slots, 1 to 8 slots: the first k slots alone return the records of
+    weighted_stats and count, sums, mean[:k] and cov[:k, :k] of weighted_covariance of the call with all eight, byte for byte.
+    4 197 columns are 66 waves, so a lane of the merge takes two waves and the lanes 33 to 63 none; the last block has 37 columns."""
+    g, x, ok = small["g"], small["rows"]["J_SUM"], small["status"] == 0
+    finite = x[ok & ~np.isnan(x)]
+    g.set_weights(J_SUM, "gauss", float(np.median(finite[finite > 0.0])) / 2.0)
+    try:
+        for group in (None, 1):
+            st8 = as_array(g.weighted_stats(SLOTS, group=group), SLOTS)
+            n8, sw8, sw28, mean8, cov8 = g.weighted_covariance(SLOTS, group=group)
+            assert n8 > 100 and st8["count"].min() == n8 and (np.diag(cov8)[:5] > 0.0).all()
+            for k in range(1, 9):
+                st = as_array(g.weighted_stats(SLOTS[:k], group=group), SLOTS[:k])
+                assert all(st[i].tobytes() == st8[i].tobytes() for i in range(k)), (group, k)
+                n, sw, sw2, mean, cov = g.weighted_covariance(SLOTS[:k], group=group)
+                assert (n, sw, sw2) == (n8, sw8, sw28) and mean.tobytes() == mean8[:k].tobytes(), (group, k)
+                assert cov.tobytes() == np.ascontiguousarray(cov8[:k, :k]).tobytes(), (group, k)
+    finally:
+        g.clear_weights()
+
+
+def test_a_second_trip_and_sixteen_waves_a_lane_are_deterministic(big):
+    """70 001 columns are 1 094 blocks on a grid of 1 024 waves: 70 waves take a second block, and a lane of every merge takes 16
+    waves.  Two consecutive calls over all columns return the same bytes (the group statistics and the covariances assert theirs
+    on such a handle in tests/test_gpu_group_stats.py and tests/test_gpu_sens.py)."""
+    g, scale = big["g"], big["scale"]
+
+    def everything():
+        info = g.set_weights(J_SUM, "gauss", scale)
+        n, sw, sw2, mean, cov = g.weighted_covariance(SLOTS)
+        return (tuple(sorted(info.items())), g.weights().tobytes(), as_array(g.weighted_stats(SLOTS), SLOTS).tobytes(),
+                g.weighted_histogram("thickness", 254, 0.5, 0.01).tobytes(), n, sw, sw2, mean.tobytes(), cov.tobytes(),
+                g.histogram("thickness", 254, 0.5, 0.01).tobytes(), g.histogram("T_top", 40, -30.0, 1.0, by_group=True).tobytes())
+    first = everything()
+    assert first[0] and dict(first[0])["n_pos"] > 1000 and first[4] > 1000
+    assert everything() == first
+
+
 def test_the_row_outlives_steps_and_uploads():
     """stepping, set_state, set_status and set_clock leave the row alone"""
     ncol = 300

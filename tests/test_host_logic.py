@@ -443,3 +443,57 @@ def test_pass_plan_tiles_every_array_once_and_marks_the_leading_passes(tmp_path)
                            "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
+
+
+SLOT_WALK_PROGRAM = r'''
+#include <cstdio>
+#include <cstdlib>
+#include "samsim_slot_walk.h"
+
+#define CHECK(c) do { if (!(c)) { std::printf("line %d: %s (ns %d, p %d)\n", __LINE__, #c, g_ns, g_p); std::exit(1); } } while (0)
+static int g_ns, g_p;
+
+int main() {
+  using namespace slot_walk;
+  int pairs = 0;
+  for (g_ns = 1; g_ns <= 8; ++g_ns) {
+    // the lane update's own loop: p advances with (i, j) over the upper triangle, row by row
+    g_p = 0;
+    for (int i = 0; i < g_ns; ++i)
+      for (int j = i; j < g_ns; ++j, ++g_p) {
+        int pi = -1, pj = -1;
+        pair_of(g_p, g_ns, pi, pj);
+        CHECK(pi == i && pj == j);
+      }
+    CHECK(g_p == g_ns * (g_ns + 1) / 2);   // exactly the upper triangle, no pair left out and none twice
+    pairs += g_p;
+  }
+  for (g_ns = 0; g_ns <= 9; ++g_ns) {
+    int reached = 0, calls = 0;
+    const bool known = dispatch_nslots(g_ns, [&](auto ns) { reached = decltype(ns)::value; ++calls; });
+    if (g_ns >= 1 && g_ns <= 8) CHECK(known && calls == 1 && reached == g_ns);
+    else CHECK(!known && calls == 0);
+  }
+  CHECK(slot_grid(1, 1024) == 1 && slot_grid(64, 1024) == 1 && slot_grid(65, 1024) == 2 && slot_grid(70001, 1024) == 1024);
+  std::printf("ok %d pairs\n", pairs);
+  return 0;
+}
+'''
+
+
+def test_slot_walk_pairs_and_dispatch(tmp_path):
+    """The plain-C++ part of samsim_slot_walk.h compiled alone by g++, once as it is and once under the address and undefined
+    behaviour sanitizers: for 1 to 8 slots pair_of(p, ns) enumerates exactly the upper triangle, row by row, in the order in which
+    the lane update's `for i, for j = i` loop advances p; dispatch_nslots reaches the instantiation NS == nslots for 1 to 8 and
+    refuses 0 and 9 without a call."""
+    import os
+    import subprocess
+    from tests.helpers import ROOT
+    src = tmp_path / "slot_walk.cpp"
+    src.write_text(SLOT_WALK_PROGRAM)
+    for flags in ([], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]):
+        exe = tmp_path / ("slot_walk_san" if flags else "slot_walk")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", *flags, "-I", os.path.join(ROOT, "samsim_amd", "csrc"),
+                               str(src), "-o", str(exe)])
+        out = subprocess.run([str(exe)], capture_output=True, text=True)
+        assert out.returncode == 0 and out.stdout.startswith("ok 120 pairs"), out.stdout + out.stderr
