@@ -498,6 +498,17 @@ MODULE mo_samsim_capi
        REAL(c_double), INTENT(out) :: sum_w, sum_w2
        REAL(c_double), INTENT(out) :: mean(*), cov(*)
      END FUNCTION
+     !> the weighted joint histogram of one layer array: wsum(nvbins + 2, nbins), entry fastest, the sum of the weights of the
+     !! columns per depth bin and value entry of samsim_get_profile_histogram (rq%narrays must be 1; group as there)
+     INTEGER(c_int) FUNCTION samsim_get_weighted_profile_histogram(h, rq, vb, group, wsum) &
+          BIND(C, name='samsim_get_weighted_profile_histogram')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(samsim_profile_request), INTENT(in) :: rq
+       TYPE(samsim_hist_bins), INTENT(in) :: vb
+       INTEGER(c_int32_t), VALUE :: group
+       REAL(c_double), INTENT(out) :: wsum(*)
+     END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')
        IMPORT

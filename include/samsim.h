@@ -857,8 +857,8 @@ int samsim_get_weighted_histogram(samsim_handle *h, int32_t slot, const samsim_h
  *   Scratch.  samsim_get_weighted_covariance stays within SAMSIM_WEIGHT_SCRATCH_BYTES (its partials lie where those of the weighted
  *     moments do).  samsim_get_weighted_profile_stats: at most SAMSIM_WPROFILE_SCRATCH_BYTES of device memory whatever ncol and the
  *     request are (the waves' partials of one pass, then the results); allocated on first use, freed by samsim_destroy.
- *   Not in scope.  Weighted profile histograms; all groups in one call; resampling or any write to the ensemble; weights in
- *     checkpoint files.
+ *   Not in scope.  All groups in one call; resampling or any write to the ensemble; weights in checkpoint files.  (The weighted
+ *     joint histogram of a profile is the entry point of the next block.)
  *   Errors, all found before any device work, in this order; a call that is refused writes nothing to the caller's buffers.
  *     samsim_get_weighted_profile_stats: SAMSIM_ERR_ARG for h, rq or out NULL; every check of samsim_get_profile_stats, in its order;
  *     no weight row; the group checks of samsim_get_covariance.  samsim_get_weighted_covariance: SAMSIM_ERR_ARG for any NULL pointer;
@@ -869,6 +869,54 @@ int samsim_get_weighted_profile_stats(samsim_handle *h, const samsim_profile_req
 int samsim_get_weighted_covariance(samsim_handle *h, int32_t nslots, const int32_t *slots, int32_t group,
                                    int64_t *count, double *sum_w, double *sum_w2,
                                    double *mean /*[nslots]*/, double *cov /*[nslots][nslots]*/);
+
+/* Posterior bands: the weight row applied to the joint histogram of a layer profile.  samsim_get_weighted_profile_histogram is
+ * samsim_get_profile_histogram with weights -- per depth bin and value entry the sum of the weights of the columns that land there
+ * --, from which the posterior median and the 5-95 % band of T(z), S_bu(z) or psi_l(z) follow on the host as quantile brackets per
+ * depth bin: the summary of a skewed, bounded posterior that mean and variance are not.  A read-only reduction: it reads status,
+ * labels, the layer block and the weight row and writes only its own scratch.  The entry point was added without a change of
+ * SAMSIM_ABI_VERSION (it stays 6): a new symbol only.
+ *
+ *   Request.  rq is a request of samsim_get_profile_stats with narrays == 1; wsum[rq->nbins][nvbins+2].  The bins, the layer value
+ *     a_k (the layer value of samsim_get_state with clamp = false and adjust = true, see "Layer value"), the per-column bin value v
+ *     and the condition under which a column contributes to a bin are exactly those of samsim_get_profile_histogram for the same rq;
+ *     the edges and the entry of a value are exactly those of samsim_get_histogram (a NaN lands in entry 0, the guessed bin is
+ *     corrected against the rounded edges).
+ *   Columns.  A column COUNTS as in samsim_get_weighted_profile_stats: its status is 0, its label passes `group` (-1: every column,
+ *     no labels needed; >= 0: only that label of samsim_set_groups; one group per call), and its weight w > 0.  A column that does
+ *     not count behaves like a stopped one.
+ *   Result.  wsum[b][i] is the sum of w over the counting columns that contribute to bin b and whose bin value lands in entry i.
+ *   Passes.  A request is served in passes of `chunk` depth bins, each a walk over the layers of every column as in the profile
+ *     statistics: passes = ceil(nbins / chunk), chunk = min(64, 64 512 / (8 * (65 + ((nvbins + 2) | 1)))) -- the walk's tile
+ *     [chunk][65], the lanes' masks, the block's 64 weights and the wave's table [chunk][(nvbins + 2) | 1] of doubles share the
+ *     64 KiB of LDS of a workgroup --: 64 up to 59 value bins, 30 at 200, 25 at SAMSIM_HIST_MAX_VBINS.
+ *   Order of summation, fixed.  A pass runs G = min(ceil(ncol / 64), 512) one-wave workgroups; wave g owns the 64-column blocks
+ *     g, g + G, ...  In a block lane j owns depth bin j of the pass and walks row j of the tile over the 64 columns, so within a wave
+ *     the weights of an entry are added in ascending column order.  Then the waves' tables are added per (bin, entry) in wave
+ *     order with one bracket: lane l of the merge takes the waves [l * per, (l + 1) * per), per = ceil(G / 64), ascending, then
+ *     the 64 lanes ascending.  No atomics of any kind; a plain sum, so no fused multiply-add either; the grid and the chunk are fixed
+ *     by ncol and nvbins alone.
+ *   Properties.  (1) Two calls on the same state return the same bytes.  (2) Relabelling or re-weighting columns outside `group`
+ *     changes nothing.  (3) When every counting column has w == 1.0, wsum is (double)counts of samsim_get_profile_histogram for the
+ *     same request and group, bit for bit; with integer-valued weights every entry is exact.  (4) wsum[b][i] > 0 exactly where at
+ *     least one counting column lands in (b, i) -- the weights are positive, so no sum of them is 0 --; every other entry is +0.0.
+ *     (5) A row's bytes do not depend on how many bins the request has: rows [0, k) of a from-top request with nbins = k are the
+ *     first k rows of the same request with a larger nbins.  (6) The entries of row b sum to sum_w of bin b of
+ *     samsim_get_weighted_profile_stats to within the rounding of the two orders of summation, and the lowest and the highest entry
+ *     of positive weight contain that call's min and max.
+ *   Like every getter the call waits for the handle's streams; it changes neither the state, the status, the clock, the output
+ *     snapshot, the labels, the tracks, the scores nor the weight row.
+ *   Scratch: at most SAMSIM_WPHIST_SCRATCH_BYTES of device memory whatever ncol and the request are -- the waves' tables of one pass,
+ *     G x chunk x (nvbins + 2) doubles (every pass reuses them), then the result, at most 1 024 x 256 doubles --; allocated on first
+ *     use, kept in the handle, freed by samsim_destroy.
+ *   Not in scope.  All groups in one call; more than one array per call; exact quantiles; resampling or any write to the ensemble;
+ *     weights in checkpoint files; the Fortran host's namelist.
+ *   Errors, all found before any device work, in this order; a call that is refused writes nothing to wsum.  SAMSIM_ERR_ARG for h,
+ *     rq, vb or wsum NULL; every check of samsim_get_profile_histogram in its order, through the vb checks (every check of
+ *     samsim_get_profile_stats; narrays != 1; the vb checks); no weight row; the group checks of samsim_get_covariance. */
+#define SAMSIM_WPHIST_SCRATCH_BYTES (32ull << 20)   /* 25 MiB of tables (512 waves x 25 bins x 256 doubles), then 2 MiB of result */
+int samsim_get_weighted_profile_histogram(samsim_handle *h, const samsim_profile_request *rq, const samsim_hist_bins *vb,
+                                          int32_t group, double *wsum /*[rq->nbins][vb->nvbins + 2]*/);
 
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);

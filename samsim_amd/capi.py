@@ -291,6 +291,42 @@ def weighted_quantile_bracket(wsum, v0, dv, q):
     return (-np.inf if i == 0 else float(e[i - 1])), (np.inf if i == wsum.size - 1 else float(e[i]))
 
 
+WPHIST_SCRATCH_BYTES = 32 << 20     # SAMSIM_WPHIST_SCRATCH_BYTES
+WPHIST_GRID = 512                   # DEV_WPHIST_GRID (samsim_pass_plan.h): the waves of a pass, which decide the merge order
+WPHIST_LDS_BYTES = 64 << 10         # DEV_WPHIST_LDS_BYTES
+
+
+def wphist_chunk(nvbins) -> int:
+    """dev_wphist_chunk (samsim_pass_plan.h): the depth bins one pass of Solver.weighted_profile_histogram serves -- the tile rows
+    [65] and the table rows [(nvbins + 2) | 1] of doubles that fit 64 KiB of LDS beside the lanes' masks and the block's weights,
+    at most 64"""
+    per_bin = (65 + ((int(nvbins) + 2) | 1)) * 8
+    return min(64, (WPHIST_LDS_BYTES - 1024) // per_bin)
+
+
+def weighted_profile_quantiles(wsum, v0, dv, qs):
+    """(lo, hi), each float64 [len(qs), nbins], from the table [nbins, nvbins + 2] of Solver.weighted_profile_histogram:
+    weighted_quantile_bracket of every row for every q of qs, so the weighted q-quantile of depth bin b lies in
+    [lo[k, b], hi[k, b]); NaN in both for a row without weight.  qs = (0.05, 0.5, 0.95) gives the posterior median and the 5-95 %
+    band of a profile"""
+    wsum = np.asarray(wsum, dtype=np.float64)
+    if wsum.ndim != 2 or wsum.shape[1] < 3:
+        raise ValueError("a table [nbins, nvbins + 2] of sums is needed")
+    if not (wsum >= 0.0).all():
+        raise ValueError("a sum of weights is negative or a NaN")
+    qs = [float(q) for q in qs]
+    if not all(0.0 <= q <= 1.0 for q in qs):
+        raise ValueError("q outside [0, 1]")
+    lo = np.full((len(qs), wsum.shape[0]), np.nan)
+    hi = np.full((len(qs), wsum.shape[0]), np.nan)
+    for b, row in enumerate(wsum):
+        if not (row > 0.0).any():
+            continue
+        for k, q in enumerate(qs):
+            lo[k, b], hi[k, b] = weighted_quantile_bracket(row, v0, dv, q)
+    return lo, hi
+
+
 def weighted_profile_mean(pair_stats) -> np.ndarray:
     """the weighted mean of the bin value y per bin, sum w y / sum w over the bin's contributing columns, from an array of
     PAIR_STAT_DTYPE that Solver.profile_regression returned with predictor=weight_slot(): mean_y + cov / mean_x (cov = mean(w y) -
@@ -578,6 +614,12 @@ class Solver:
                      "get_weighted_covariance": [vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]}
         for n, a in wprof_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the weighted joint histogram of a profile
+        wphist_sig = {"get_weighted_profile_histogram": [vp, C.POINTER(ProfileRequest), C.POINTER(HistBins), C.c_int32, C.c_void_p]}
+        for n, a in wphist_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -1095,6 +1137,23 @@ class Solver:
         rq = self._profile_request(names, axis, origin, nbins, z0, dz)
         out = self.weighted_profile_stats_raw(rq, -1 if group is None else int(group))
         return {n: out[i] for i, n in enumerate(names)}
+
+    def weighted_profile_histogram_raw(self, rq: ProfileRequest, vb: HistBins, group=-1) -> np.ndarray:
+        """samsim_get_weighted_profile_histogram with the arguments as given (no checks on this side): float64 [nbins, nvbins+2]"""
+        buf = np.zeros((max(1, min(rq.nbins, PROFILE_MAX_BINS)), max(0, min(vb.nvbins, HIST_MAX_VBINS)) + 2))
+        self._chk(self._f("get_weighted_profile_histogram")(self._h, C.byref(rq), C.byref(vb), int(group), buf.ctypes.data),
+                  "get_weighted_profile_histogram")
+        return buf
+
+    def weighted_profile_histogram(self, name, nvbins, v0, dv, axis="layer", origin="top", nbins=None, z0=0.0, dz=None,
+                                   group=None) -> np.ndarray:
+        """the sum of the weights per depth bin x value entry of profile_histogram() over the running columns with a positive weight
+        -- with group: of those with that label -- (samsim_get_weighted_profile_histogram): float64 [nbins, nvbins+2];
+        capi.weighted_profile_quantiles reads the posterior median and band of the profile off it"""
+        if axis == "depth" and (nbins is None or dz is None):
+            raise ValueError("axis='depth' needs nbins and dz")
+        rq = self._profile_request([name], axis, origin, nbins, z0, dz)
+        return self.weighted_profile_histogram_raw(rq, hist_bins(nvbins, v0, dv), -1 if group is None else int(group))
 
     def weighted_covariance_raw(self, slots, group=-1):
         """samsim_get_weighted_covariance with the arguments as given (no checks on this side): (count, sum_w, sum_w2, mean [nslots],

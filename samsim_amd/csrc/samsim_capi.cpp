@@ -24,6 +24,7 @@
 #include "samsim_sens.h"
 #include "samsim_tracks.h"
 #include "samsim_weights.h"
+#include "samsim_wphist.h"
 #include "samsim_wprofile.h"
 
 extern "C" hipError_t samsim_launch_step(const DevParams *d_params, const DevParams *hp, long long grid, hipStream_t stream);
@@ -90,6 +91,7 @@ struct samsim_handle {
   double *weight_row = nullptr; // [ncol] weights of the columns (samsim_set_weights), changed by that call alone
   void *d_weight = nullptr;    // samsim_set_weights and the weighted reductions: the waves' tables and partials, then the results (kWeightScratch bytes)
   void *d_wprof = nullptr;     // samsim_get_weighted_profile_stats: the waves' partials of one pass, then the results (kWProfScratch bytes)
+  void *d_wphist = nullptr;    // samsim_get_weighted_profile_histogram: the waves' tables of one pass, then the result (kWPHistScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -255,6 +257,10 @@ static_assert(sizeof(samsim_weight_spec) == 32 && sizeof(samsim_weight_info) == 
 // device scratch of the weighted profile statistics: the waves' partials of one pass, then the results of the largest request
 constexpr size_t kWProfScratch = DEV_WPROF_BYTES;
 static_assert(kWProfScratch <= SAMSIM_WPROFILE_SCRATCH_BYTES && SAMSIM_WPROFILE_SCRATCH_BYTES <= (16ull << 20), "weighted profile scratch bound of samsim.h");
+
+// device scratch of the weighted joint histogram: the waves' tables of one pass, then the result of the largest request
+constexpr size_t kWPHistScratch = DEV_WPHIST_BYTES;
+static_assert(kWPHistScratch <= SAMSIM_WPHIST_SCRATCH_BYTES && SAMSIM_WPHIST_SCRATCH_BYTES <= (64ull << 20), "weighted profile histogram scratch bound of samsim.h");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -695,7 +701,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->groups); (void)hipFree(h->d_group); (void)hipFree(h->d_hist); (void)hipFree(h->d_sens); (void)hipFree(h->tracks);
   (void)hipFree(h->func_rows);
   (void)hipFree(h->score_rows);
-  (void)hipFree(h->weight_row); (void)hipFree(h->d_weight); (void)hipFree(h->d_wprof);
+  (void)hipFree(h->weight_row); (void)hipFree(h->d_weight); (void)hipFree(h->d_wprof); (void)hipFree(h->d_wphist);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -1854,6 +1860,33 @@ int samsim_get_weighted_profile_stats(samsim_handle *h, const samsim_profile_req
   });
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(samsim_wstat) * (size_t)rq->narrays * (size_t)rq->nbins, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_get_weighted_profile_histogram(samsim_handle *h, const samsim_profile_request *rq, const samsim_hist_bins *vb, int32_t group,
+                                          double *wsum) {
+  // every check first: nothing below touches the device before the request is known to be good
+  if (!h || !rq || !vb || !wsum) return SAMSIM_ERR_ARG;
+  int rc = check_profile_request(h, rq);
+  if (rc) return rc;
+  if (rq->narrays != 1) return SAMSIM_ERR_ARG;
+  HistEdges e;
+  rc = check_hist_bins(vb, &e);
+  if (rc) return rc;
+  if (!h->weight_row) return SAMSIM_ERR_ARG;
+  if (!good_group(h, group)) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(scratch(&h->d_wphist, kWPHistScratch));
+  double *d_tables = (double *)h->d_wphist;
+  double *d_out = (double *)((char *)h->d_wphist + DEV_WPHIST_PART_BYTES);
+  // a pass's merge writes its own rows of the result, every entry of them
+  rc = for_each_pass(h, rq, group, dev_wphist_chunk(e.nvbins), [&](const ProfPass &p, size_t) {
+    return samsim_launch_weighted_profile_hist(p, h->weight_row, e, d_tables, d_out, h->stream);
+  });
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(wsum, d_out, sizeof(double) * (size_t)rq->nbins * (size_t)(e.nvbins + 2), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return SAMSIM_OK;
 }

@@ -33,4 +33,24 @@ static inline int dev_hist_chunk(int nvbins) {
   return c < DEV_PROF_BINS ? c : DEV_PROF_BINS;
 }
 
+// The chunk of a pass of the weighted joint histogram (samsim_wphist.h): the same rule with a table of doubles -- the depth bins
+// whose tile rows and table rows [(nvbins + 2) | 1] fit the LDS of a one-wave workgroup beside the lanes' masks and the block's 64
+// weights.  64 up to 59 value bins, 25 at SAMSIM_HIST_MAX_VBINS.  A request runs at most DEV_WPHIST_GRID waves, whatever ncol is:
+// the number of waves decides the merge order and so the bytes, and with the chunk it bounds the waves' tables of a pass.
+#define DEV_WPHIST_LDS_BYTES (64 << 10)
+#ifndef DEV_WPHIST_GRID   // (a measuring build of the library may set another; the product is this line)
+#define DEV_WPHIST_GRID 512
+#endif
+constexpr int dev_wphist_row_stride(int nvbins) { return (nvbins + 2) | 1; }
+constexpr int dev_wphist_chunk(int nvbins) {
+  const int per_bin = (DEV_PROF_BINS + 1 + dev_wphist_row_stride(nvbins)) * (int)sizeof(double);
+  const int c = (DEV_WPHIST_LDS_BYTES - 64 * (int)sizeof(unsigned long long) - 64 * (int)sizeof(double)) / per_bin;
+  return c < DEV_PROF_BINS ? c : DEV_PROF_BINS;
+}
+// LDS bytes of a pass, and the doubles of one wave's table in device memory [chunk][nvbins + 2]
+constexpr long long dev_wphist_lds(int nvbins) {
+  return (long long)dev_wphist_chunk(nvbins) * (DEV_PROF_BINS + 1 + dev_wphist_row_stride(nvbins)) * (long long)sizeof(double) + 1024;
+}
+constexpr long long dev_wphist_wave_doubles(int nvbins) { return (long long)dev_wphist_chunk(nvbins) * (nvbins + 2); }
+
 #endif
