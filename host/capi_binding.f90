@@ -145,6 +145,22 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: sum_w, sum_w2, mean, var, min, max
   END TYPE samsim_wstat
 
+  ! samsim_resample: the offspring row as a slot, enum samsim_resample_kind, the draw and what the call reports of it (Fortran has
+  ! no unsigned kind: seed carries the bits of the uint64_t)
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_OFFSPRING_SLOT = 327680_c_int32_t
+  INTEGER(c_int64_t), PARAMETER :: SAMSIM_RESAMPLE_MAX_DRAWS = 4194304_c_int64_t
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_RESAMPLE_SYSTEMATIC = 0, SAMSIM_RESAMPLE_STRATIFIED = 1
+  TYPE, BIND(C) :: samsim_resample_spec
+     INTEGER(c_int32_t) :: struct_size, kind, group, reserved      ! group -1 = any
+     INTEGER(c_int64_t) :: m
+     REAL(c_double)     :: u0
+     INTEGER(c_int64_t) :: seed
+  END TYPE samsim_resample_spec
+  TYPE, BIND(C) :: samsim_resample_info
+     INTEGER(c_int64_t) :: n_pos, m_drawn, n_survivors, max_offspring, argmax_offspring
+     REAL(c_double)     :: sum_w
+  END TYPE samsim_resample_info
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -508,6 +524,28 @@ MODULE mo_samsim_capi
        TYPE(samsim_hist_bins), INTENT(in) :: vb
        INTEGER(c_int32_t), VALUE :: group
        REAL(c_double), INTENT(out) :: wsum(*)
+     END FUNCTION
+     !> draw spec%m members by the weight row: the offspring row (SAMSIM_OFFSPRING_SLOT is then a slot of the ensemble reductions) and
+     !! the ascending ancestor list; nothing of the ensemble is written; spec = c_null_ptr (with info = c_null_ptr) removes the rows
+     INTEGER(c_int) FUNCTION samsim_resample(h, spec, info) BIND(C, name='samsim_resample')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       TYPE(c_ptr), VALUE :: spec                        ! samsim_resample_spec (c_loc of a TARGET), or c_null_ptr
+       TYPE(c_ptr), VALUE :: info                        ! samsim_resample_info (c_loc of a TARGET), or c_null_ptr
+     END FUNCTION
+     !> the window [col0, col0 + ncols) of the offspring row
+     INTEGER(c_int) FUNCTION samsim_get_offspring(h, col0, ncols, out) BIND(C, name='samsim_get_offspring')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: col0, ncols
+       REAL(c_double), INTENT(out) :: out(*)
+     END FUNCTION
+     !> the 0-based column indices of the ancestors of the draws [k0, k0 + nk), ascending
+     INTEGER(c_int) FUNCTION samsim_get_ancestors(h, k0, nk, out) BIND(C, name='samsim_get_ancestors')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: k0, nk
+       INTEGER(c_int64_t), INTENT(out) :: out(*)
      END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')

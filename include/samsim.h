@@ -918,6 +918,77 @@ int samsim_get_weighted_covariance(samsim_handle *h, int32_t nslots, const int32
 int samsim_get_weighted_profile_histogram(samsim_handle *h, const samsim_profile_request *rq, const samsim_hist_bins *vb,
                                           int32_t group, double *wsum /*[rq->nbins][vb->nvbins + 2]*/);
 
+/* Posterior draws: the ensemble resampled by its weights, indices only.  A scored ensemble run as a particle filter drops the members
+ * the data rule out and continues from copies of the ones they support; samsim_resample says which members to continue from and how
+ * many copies of each, without a download of the weight row.  It is a read-only reduction like its predecessors: it reads the weight
+ * row, status and the labels and writes two rows of its own -- per column the number of offspring, per draw the ancestor's column
+ * index -- and its scratch.  Moving state stays with samsim_get_columns (which takes the ancestor list, duplicates allowed) and
+ * samsim_set_state.  The entry points were added without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only.
+ *
+ *   Columns.  A column COUNTS as in samsim_get_weighted_stats: its status is 0, its label passes `group` (-1: every column, no
+ *     labels needed; >= 0: only that label of samsim_set_groups; one group per call), and its weight w > 0.  Its term is w; the
+ *     term of a column that does not count is +0.0.
+ *   The cumulative weight C_c: the inclusive prefix sum of the terms in ascending column order, in one bracketing.  The nblk =
+ *     ceil(ncol / 64) 64-column blocks are cut into G = ceil(nblk / per) contiguous ranges of per = ceil(nblk / 1024) blocks (the
+ *     grid rule of samsim_select_columns: range order is column order).  Inside range g the local sum L_c runs sequentially, column
+ *     after column, from 0.0; T_g is the range's last L; B_0 = 0.0 and B_{g+1} = B_g + T_g, sequentially; C_c = B_g + L_c; W = B_G,
+ *     which is the last column's C by construction.  With this bracketing C does not decrease in c in floating point (a tree-shaped
+ *     scan inside a block would not guarantee that).  No fused multiply-add anywhere.
+ *   The draw coordinate: t_c = (C_c / W) * m, one IEEE division, then one product; t_{-1} = 0.  The last counting column has
+ *     t == m exactly.
+ *   The point count K(t), the number of draw points below t: K(t) = m if t >= m; else
+ *       SAMSIM_RESAMPLE_SYSTEMATIC (points u0 + k): K(t) = min(max(ceil(t - u0), 0), m), the difference rounded;
+ *       SAMSIM_RESAMPLE_STRATIFIED (points k + u(k)): f = floor(t), K(t) = f + (u(f) < t - f), with u(k) = (mix(seed, k) >> 11) * 2^-53
+ *         and mix the splitmix64 finaliser of seed + (k + 1) * 0x9E3779B97F4A7C15: z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ *         z *= 0x94D049BB133111EB, z ^= z >> 31, in wrapping 64-bit arithmetic.
+ *     Both K do not decrease in t.
+ *   Offspring and ancestors.  N_c = K(t_c) - K(t_{c-1}) is the column's number of offspring, stored as a double in the offspring row
+ *     [ncol]; its copies are ancestors[K(t_{c-1}) .. K(t_c)).  The ancestor list is ascending and has exactly m entries; a column
+ *     that does not count never appears in it.  m may be below, equal to or above the number of columns.
+ *   No draw.  W == 0 or W not finite: every offspring is 0, m_drawn = 0, sum_w reports W, and the call returns 0.
+ *   info (may be NULL).  n_pos the counting columns, sum_w = W, m_drawn the entries of the ancestor list (m, or 0), n_survivors the
+ *     columns with N_c >= 1, max_offspring the largest N_c and argmax_offspring the lowest column index that has it (0 without a
+ *     draw).  All integer reductions; no atomics of any kind.
+ *   Lifetime.  The offspring row (doubles, ncol) and the ancestor list (int64, grown to the largest m asked for) are allocated by the
+ *     first successful call; a later call replaces their contents; samsim_resample(h, NULL, NULL) or samsim_destroy frees them.
+ *     Stepping, uploads and samsim_set_weights leave the rows alone, and there is no dirty flag: the rows describe the weights as
+ *     they were at the call.  They are not part of a checkpoint.  A call that is refused leaves the previous rows in force and writes
+ *     nothing to the caller's buffers.
+ *   samsim_get_offspring takes windows inside [0, ncol), samsim_get_ancestors windows inside [0, m_drawn) of the last call.
+ *   Slot.  While the offspring row exists SAMSIM_OFFSPRING_SLOT is accepted wherever a slot is -- the survivors through
+ *     samsim_select_columns on offspring >= 1, the histogram of the family sizes, the survivors per site through the group
+ *     statistics --; without it, it is the SAMSIM_ERR_ARG of any bad slot.
+ *   Properties.  Two calls return the same bytes; the sum of the offspring row is m_drawn; relabelling columns outside `group`
+ *     changes nothing; |N_c - m w_c / W| is at most 1 (SYSTEMATIC) and below 2 (STRATIFIED) up to the rounding of C.
+ *   Scratch: SAMSIM_RESAMPLE_SCRATCH_BYTES of device memory whatever ncol and m are -- the ranges' sums, bases and integer partials,
+ *     then the result --, allocated on first use and freed by samsim_destroy; the two rows are not counted in it.
+ *   Not in scope.  Any write to the ensemble, or a device-side copy of columns; multinomial or residual resampling; a draw across
+ *     the handles of several ranks (each rank resamples its own shard; a global draw needs the ranks' W, which info returns); the
+ *     Fortran host's namelist.
+ *   Errors, all found before any device work, in this order.  samsim_resample: SAMSIM_ERR_ARG for h NULL; with spec NULL: info not
+ *     NULL is SAMSIM_ERR_ARG, else the rows are removed (also when there are none); SAMSIM_ERR_ABI for a wrong struct_size;
+ *     SAMSIM_ERR_ARG for a bad kind; no weight row; the group checks of samsim_get_covariance; m outside
+ *     1..SAMSIM_RESAMPLE_MAX_DRAWS; SYSTEMATIC with u0 outside [0, 1) or a NaN, or with seed != 0; STRATIFIED with u0 != 0;
+ *     reserved != 0; SAMSIM_ERR_NOMEM if a row cannot be allocated.  samsim_get_offspring, samsim_get_ancestors: SAMSIM_ERR_ARG for
+ *     NULL pointers; no rows; a window outside the range. */
+#define SAMSIM_OFFSPRING_SLOT 0x50000
+#define SAMSIM_RESAMPLE_MAX_DRAWS 4194304
+#define SAMSIM_RESAMPLE_SCRATCH_BYTES (64ull << 10)   /* partials only; a constant whatever ncol and m are */
+enum samsim_resample_kind { SAMSIM_RESAMPLE_SYSTEMATIC = 0, SAMSIM_RESAMPLE_STRATIFIED = 1 };
+typedef struct samsim_resample_spec {   /* 40 bytes */
+  int32_t struct_size, kind, group, reserved;
+  int64_t m;          /* draws, 1..SAMSIM_RESAMPLE_MAX_DRAWS */
+  double  u0;         /* SYSTEMATIC: the offset, 0 <= u0 < 1; STRATIFIED: must be 0 */
+  uint64_t seed;      /* STRATIFIED: the seed of the per-draw offsets; SYSTEMATIC: must be 0 */
+} samsim_resample_spec;
+typedef struct samsim_resample_info {   /* 48 bytes */
+  int64_t n_pos, m_drawn, n_survivors, max_offspring, argmax_offspring;
+  double  sum_w;
+} samsim_resample_info;
+int samsim_resample(samsim_handle *h, const samsim_resample_spec *spec, samsim_resample_info *info /* or NULL */);
+int samsim_get_offspring(samsim_handle *h, int64_t col0, int64_t ncols, double *out /*[ncols]*/);
+int samsim_get_ancestors(samsim_handle *h, int64_t k0, int64_t nk, int64_t *out /*[nk]*/);
+
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);
 int samsim_abi_version(void);

@@ -270,6 +270,36 @@ def weight_slot() -> int:
     return 0x40000
 
 
+# enum samsim_resample_kind
+RESAMPLE_KINDS = {"systematic": 0, "stratified": 1}
+RESAMPLE_MAX_DRAWS = 4194304    # SAMSIM_RESAMPLE_MAX_DRAWS
+
+
+class ResampleSpec(C.Structure):
+    """samsim_resample_spec: m draws over the columns that count (status 0, label `group` or -1 for any, w > 0), "systematic" with
+    the offset u0 in [0, 1) or "stratified" with the seed of the per-draw offsets"""
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("group", C.c_int32), ("reserved", C.c_int32), ("m", C.c_int64),
+                ("u0", C.c_double), ("seed", C.c_uint64)]
+
+    @staticmethod
+    def make(m, kind="systematic", u0=0.0, seed=0, group=None) -> "ResampleSpec":
+        """kind from RESAMPLE_KINDS or its number; u0 belongs to "systematic", seed to "stratified" (the other's field is 0)"""
+        k = RESAMPLE_KINDS[kind] if isinstance(kind, str) else int(kind)
+        return ResampleSpec(C.sizeof(ResampleSpec), k, -1 if group is None else int(group), 0, int(m), float(u0), int(seed))
+
+
+class ResampleInfo(C.Structure):
+    """samsim_resample_info"""
+    _fields_ = [("n_pos", C.c_int64), ("m_drawn", C.c_int64), ("n_survivors", C.c_int64), ("max_offspring", C.c_int64),
+                ("argmax_offspring", C.c_int64), ("sum_w", C.c_double)]
+
+
+def offspring_slot() -> int:
+    """SAMSIM_OFFSPRING_SLOT: the offspring row of resample as a slot of ensemble_stats, group_stats, histogram, covariance and
+    select, while the row exists"""
+    return 0x50000
+
+
 def weighted_quantile_bracket(wsum, v0, dv, q):
     """(lo, hi) with the weighted q-quantile of the data in [lo, hi), from the sums of Solver.weighted_histogram (nvbins + 2
     entries): the quantile is the smallest value whose cumulative weight reaches q times the total; i = the first entry of positive
@@ -338,7 +368,8 @@ def weighted_profile_mean(pair_stats) -> np.ndarray:
 
 
 def _slot(name) -> int:
-    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot, func_slot, score_slot or weight_slot gives it"""
+    """the slot of a name from SCALARS, of "N_active", or of an int as track_slot, func_slot, score_slot, weight_slot or offspring_slot
+    gives it"""
     if isinstance(name, (int, np.integer)):
         return int(name)
     return -1 if name == "N_active" else S[name]
@@ -620,6 +651,13 @@ class Solver:
         # and the weighted joint histogram of a profile
         wphist_sig = {"get_weighted_profile_histogram": [vp, C.POINTER(ProfileRequest), C.POINTER(HistBins), C.c_int32, C.c_void_p]}
         for n, a in wphist_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the posterior draw
+        resample_sig = {"resample": [vp, C.POINTER(ResampleSpec), C.POINTER(ResampleInfo)], "get_offspring": [vp, i64, i64, C.c_void_p],
+                        "get_ancestors": [vp, i64, i64, C.c_void_p]}
+        for n, a in resample_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -1174,6 +1212,53 @@ class Solver:
         -- (samsim_get_weighted_covariance): weighted means and weighted population covariances, the diagonal the variances of
         weighted_stats; capi.correlation(cov) gives the correlations"""
         return self.weighted_covariance_raw([_slot(n) for n in names], -1 if group is None else int(group))
+
+    # -- the posterior draw: which members to continue from, and how many copies of each
+    def resample_raw(self, spec, info=None):
+        """samsim_resample with the arguments as given (no checks on this side): spec a ResampleSpec or None, info a ResampleInfo or
+        None"""
+        self._chk(self._f("resample")(self._h, None if spec is None else C.byref(spec), None if info is None else C.byref(info)),
+                  "resample")
+        if spec is None:
+            self.m_drawn = 0
+        elif info is not None:
+            self.m_drawn = int(info.m_drawn)
+
+    def resample(self, m, kind="systematic", u0=0.0, seed=0, group=None):
+        """draw m members by the weight row over the running columns with a positive weight -- with group: of those with that label
+        -- on the device (samsim_resample): "systematic" with the offset u0 in [0, 1), or "stratified" with per-draw offsets from
+        `seed`.  offspring() then holds the copies of every column, ancestors() the ascending list of the m ancestors, and
+        offspring_slot() is the offspring row wherever a slot is accepted.  Nothing of the ensemble is written.  Returns {"n_pos",
+        "m_drawn", "n_survivors", "max_offspring", "argmax_offspring", "sum_w"}; m_drawn is 0 when no weight is positive and finite"""
+        info = ResampleInfo()
+        self.resample_raw(ResampleSpec.make(m, kind, u0, seed, group), info)
+        return {"n_pos": int(info.n_pos), "m_drawn": int(info.m_drawn), "n_survivors": int(info.n_survivors),
+                "max_offspring": int(info.max_offspring), "argmax_offspring": int(info.argmax_offspring), "sum_w": info.sum_w}
+
+    def clear_resample(self):
+        """remove the offspring row and the ancestor list (samsim_resample with NULL), also when there are none"""
+        self.resample_raw(None)
+
+    def offspring(self, col0: int = 0, ncols: int | None = None) -> np.ndarray:
+        """float64 [ncols]: the number of offspring of the columns [col0, col0 + ncols) (samsim_get_offspring)"""
+        n = self.ncol - col0 if ncols is None else ncols
+        buf = np.zeros(max(0, n))
+        self._chk(self._f("get_offspring")(self._h, col0, n, buf.ctypes.data), "get_offspring")
+        return buf
+
+    def ancestors(self, k0: int = 0, nk: int | None = None) -> np.ndarray:
+        """int64 [nk]: the ancestors of the draws [k0, k0 + nk), ascending (samsim_get_ancestors); nk None: up to the last draw of
+        the last resample() of this Solver"""
+        n = getattr(self, "m_drawn", 0) - k0 if nk is None else nk
+        buf = np.zeros(max(1, n), dtype=np.int64)
+        self._chk(self._f("get_ancestors")(self._h, k0, n, buf.ctypes.data), "get_ancestors")
+        return buf[:max(0, n)]
+
+    def resampled_columns(self, k0, nk, narr: int = NARR, with_status=False):
+        """the state of the ancestors of the draws [k0, k0 + nk), nk at most SELECT_MAX_OUT, position j holding the ancestor of draw
+        k0 + j: get_columns of that window of the ancestor list, ready for set_state of this or another Solver"""
+        assert 0 <= nk <= SELECT_MAX_OUT
+        return self.get_columns(self.ancestors(k0, nk), narr, with_status)
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

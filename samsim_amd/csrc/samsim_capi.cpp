@@ -19,6 +19,7 @@
 #include "samsim_groups.h"
 #include "samsim_hist.h"
 #include "samsim_pass_plan.h"
+#include "samsim_resample.h"
 #include "samsim_select.h"
 #include "samsim_sensors.h"
 #include "samsim_sens.h"
@@ -92,6 +93,10 @@ struct samsim_handle {
   void *d_weight = nullptr;    // samsim_set_weights and the weighted reductions: the waves' tables and partials, then the results (kWeightScratch bytes)
   void *d_wprof = nullptr;     // samsim_get_weighted_profile_stats: the waves' partials of one pass, then the results (kWProfScratch bytes)
   void *d_wphist = nullptr;    // samsim_get_weighted_profile_histogram: the waves' tables of one pass, then the result (kWPHistScratch bytes)
+  double *offspring_row = nullptr;   // [ncol] offspring of the columns (samsim_resample), changed by that call alone
+  long long *ancestors = nullptr;    // [ancestors_cap] the ancestor of every draw, the first m_drawn entries valid
+  long long ancestors_cap = 0, m_drawn = 0;
+  void *d_resample = nullptr;  // samsim_resample: the ranges' sums, bases and partials, then the result (kResampleScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -261,6 +266,9 @@ static_assert(kWProfScratch <= SAMSIM_WPROFILE_SCRATCH_BYTES && SAMSIM_WPROFILE_
 // device scratch of the weighted joint histogram: the waves' tables of one pass, then the result of the largest request
 constexpr size_t kWPHistScratch = DEV_WPHIST_BYTES;
 static_assert(kWPHistScratch <= SAMSIM_WPHIST_SCRATCH_BYTES && SAMSIM_WPHIST_SCRATCH_BYTES <= (64ull << 20), "weighted profile histogram scratch bound of samsim.h");
+// samsim_resample: the ranges' sums, bases and integer partials, then the result (samsim_resample.h); the two rows are the handle's own
+constexpr size_t kResampleScratch = DEV_RS_BYTES;
+static_assert(kResampleScratch <= SAMSIM_RESAMPLE_SCRATCH_BYTES, "resample scratch bound of samsim.h");
 
 // fill a [rows][ncol] device block with one value per row-set
 __global__ void fill_rows(double *dst, size_t n, double v) {
@@ -445,7 +453,7 @@ int launch(samsim_handle *h, long long nsteps) {
 
 // a slot of the statistics: an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE, SAMSIM_TRACK_SLOT(track, field) of the tracks in force, or
 // SAMSIM_FUNC_SLOT(i) of the functionals in force, or SAMSIM_SCORE_SLOT(field) while sensors are set, or SAMSIM_WEIGHT_SLOT while the
-// weight row exists
+// weight row exists, or SAMSIM_OFFSPRING_SLOT while the offspring row does
 bool func_slot(int32_t slot) { return slot >= SAMSIM_FUNC_SLOT(0) && slot < SAMSIM_FUNC_SLOT(SAMSIM_MAX_FUNCTIONALS); }
 bool score_slot(int32_t slot) { return slot >= SAMSIM_SCORE_SLOT(0) && slot < SAMSIM_SCORE_SLOT(SAMSIM_NSF); }
 bool good_slot(const samsim_handle *h, int32_t slot) {
@@ -453,6 +461,7 @@ bool good_slot(const samsim_handle *h, int32_t slot) {
   if (func_slot(slot)) return h->func_rows && slot - SAMSIM_FUNC_SLOT(0) < h->nfunc;
   if (score_slot(slot)) return h->score_rows != nullptr;
   if (slot == SAMSIM_WEIGHT_SLOT) return h->weight_row != nullptr;
+  if (slot == SAMSIM_OFFSPRING_SLOT) return h->offspring_row != nullptr;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks && o >= 0 && o / 32 < h->ntracks && o % 32 < SAMSIM_NTF;
 }
@@ -463,6 +472,7 @@ const double *slot_row(const samsim_handle *h, int32_t slot) {
   if (func_slot(slot)) return h->func_rows + (size_t)(slot - SAMSIM_FUNC_SLOT(0)) * (size_t)h->ncol;
   if (score_slot(slot)) return h->score_rows + (size_t)(slot - SAMSIM_SCORE_SLOT(0)) * (size_t)h->ncol;
   if (slot == SAMSIM_WEIGHT_SLOT) return h->weight_row;
+  if (slot == SAMSIM_OFFSPRING_SLOT) return h->offspring_row;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks + ((size_t)(o / 32) * SAMSIM_NTF + (size_t)(o % 32)) * (size_t)h->ncol;
 }
@@ -702,6 +712,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->func_rows);
   (void)hipFree(h->score_rows);
   (void)hipFree(h->weight_row); (void)hipFree(h->d_weight); (void)hipFree(h->d_wprof); (void)hipFree(h->d_wphist);
+  (void)hipFree(h->offspring_row); (void)hipFree(h->ancestors); (void)hipFree(h->d_resample);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -1907,6 +1918,95 @@ int samsim_get_weighted_covariance(samsim_handle *h, int32_t nslots, const int32
   if (rc) return rc;
   *sum_w = res.sum_w;
   *sum_w2 = res.sum_w2;
+  return SAMSIM_OK;
+}
+
+int samsim_resample(samsim_handle *h, const samsim_resample_spec *spec, samsim_resample_info *info) {
+  // every check first, in the order samsim.h gives: a call that is refused leaves the previous rows in force
+  if (!h) return SAMSIM_ERR_ARG;
+  if (!spec) {
+    if (info) return SAMSIM_ERR_ARG;
+    int rc = use(h);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->offspring_row); (void)hipFree(h->ancestors);
+    h->offspring_row = nullptr; h->ancestors = nullptr;
+    h->ancestors_cap = 0; h->m_drawn = 0;
+    return SAMSIM_OK;
+  }
+  if (spec->struct_size != (int32_t)sizeof(samsim_resample_spec)) return SAMSIM_ERR_ABI;
+  if (spec->kind != SAMSIM_RESAMPLE_SYSTEMATIC && spec->kind != SAMSIM_RESAMPLE_STRATIFIED) return SAMSIM_ERR_ARG;
+  if (!h->weight_row) return SAMSIM_ERR_ARG;
+  if (!good_group(h, spec->group)) return SAMSIM_ERR_ARG;
+  if (spec->m < 1 || spec->m > SAMSIM_RESAMPLE_MAX_DRAWS) return SAMSIM_ERR_ARG;
+  if (spec->kind == SAMSIM_RESAMPLE_SYSTEMATIC && (!(spec->u0 >= 0.0 && spec->u0 < 1.0) || spec->seed != 0)) return SAMSIM_ERR_ARG;
+  if (spec->kind == SAMSIM_RESAMPLE_STRATIFIED && spec->u0 != 0.0) return SAMSIM_ERR_ARG;
+  if (spec->reserved != 0) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  // the rows of the first call, kept and rewritten by the later ones; the list grows to the largest m asked for, and the one in
+  // force goes only once its successor stands
+  double *row = h->offspring_row;
+  long long *list = h->ancestors;
+  if (!row && dalloc(&row, (size_t)h->ncol) != hipSuccess) {
+    (void)hipGetLastError();
+    return SAMSIM_ERR_NOMEM;
+  }
+  if (spec->m > h->ancestors_cap && dalloc(&list, (size_t)spec->m) != hipSuccess) {
+    (void)hipGetLastError();
+    if (!h->offspring_row) (void)hipFree(row);
+    return SAMSIM_ERR_NOMEM;
+  }
+  if (!hip_ok(scratch(&h->d_resample, kResampleScratch), "hipMalloc resample scratch")) {
+    if (!h->offspring_row) (void)hipFree(row);
+    if (list != h->ancestors) (void)hipFree(list);
+    return SAMSIM_ERR_HIP;
+  }
+  h->offspring_row = row;
+  if (list != h->ancestors) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    (void)hipFree(h->ancestors);
+    h->ancestors = list;
+    h->ancestors_cap = spec->m;
+  }
+  h->m_drawn = 0;   // until the draw below stands
+  const RsGrid grid = rs_grid(h->ncol);
+  RsParams p{};
+  p.cs = col_set(h, spec->group);
+  p.w = h->weight_row;
+  p.per = grid.per; p.ranges = grid.ranges;
+  p.m = spec->m; p.u0 = spec->u0; p.seed = spec->seed; p.kind = spec->kind;
+  HIPCHK(samsim_launch_resample(&p, h->d_resample, h->offspring_row, h->ancestors, h->stream));
+  RsResult res;
+  HIPCHK(hipMemcpyAsync(&res, (const char *)h->d_resample + DEV_RS_RESULT_AT, sizeof(RsResult), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->m_drawn = res.m_drawn;
+  if (info) *info = samsim_resample_info{res.n_pos, res.m_drawn, res.n_surv, res.max_n, res.argmax, res.sum_w};
+  return SAMSIM_OK;
+}
+
+int samsim_get_offspring(samsim_handle *h, int64_t col0, int64_t ncols, double *out) {
+  if (!h || !out) return SAMSIM_ERR_ARG;
+  if (!h->offspring_row) return SAMSIM_ERR_ARG;
+  int rc = check_window(h, col0, ncols);
+  if (rc) return rc;
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  HIPCHK(hipMemcpy(out, h->offspring_row + (size_t)col0, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+int samsim_get_ancestors(samsim_handle *h, int64_t k0, int64_t nk, int64_t *out) {
+  if (!h || !out) return SAMSIM_ERR_ARG;
+  if (!h->offspring_row) return SAMSIM_ERR_ARG;
+  if (k0 < 0 || nk < 0 || k0 > h->m_drawn || nk > h->m_drawn - k0) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (nk == 0) return SAMSIM_OK;
+  HIPCHK(hipMemcpy(out, h->ancestors + (size_t)k0, sizeof(int64_t) * (size_t)nk, hipMemcpyDeviceToHost));
   return SAMSIM_OK;
 }
 
