@@ -161,6 +161,12 @@ MODULE mo_samsim_capi
      REAL(c_double)     :: sum_w
   END TYPE samsim_resample_info
 
+  ! samsim_copy_columns / samsim_apply_resample: what is copied beside the state, and what the plan reports
+  INTEGER(c_int32_t), PARAMETER :: SAMSIM_COPY_FORCING = 1, SAMSIM_COPY_TRACKS = 2, SAMSIM_COPY_SCORES = 4
+  TYPE, BIND(C) :: samsim_apply_info
+     INTEGER(c_int64_t) :: n_pool, n_free, n_copies, n_sources
+  END TYPE samsim_apply_info
+
   INTERFACE
      INTEGER(c_int) FUNCTION samsim_create(cfg, ncol, device, h) BIND(C, name='samsim_create')
        IMPORT
@@ -546,6 +552,30 @@ MODULE mo_samsim_capi
        TYPE(c_ptr), VALUE :: h
        INTEGER(c_int64_t), VALUE :: k0, nk
        INTEGER(c_int64_t), INTENT(out) :: out(*)
+     END FUNCTION
+     !> overwrite column dst(k) with column src(k) on the device (0-based indices): the bytes of samsim_get_columns -> samsim_set_state
+     !! -> samsim_set_status; what = a sum of SAMSIM_COPY_FORCING, SAMSIM_COPY_TRACKS, SAMSIM_COPY_SCORES
+     INTEGER(c_int) FUNCTION samsim_copy_columns(h, n, src, dst, what) BIND(C, name='samsim_copy_columns')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: n
+       INTEGER(c_int64_t), INTENT(in) :: src(*), dst(*)
+       INTEGER(c_int32_t), VALUE :: what
+     END FUNCTION
+     !> put the copies of the last samsim_resample where the dropped members were; SAMSIM_ERR_UNSUPPORTED, and nothing written, unless
+     !! the draw had as many members as the pool and every drawn column still runs
+     INTEGER(c_int) FUNCTION samsim_apply_resample(h, what, info) BIND(C, name='samsim_apply_resample')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int32_t), VALUE :: what
+       TYPE(c_ptr), VALUE :: info                        ! samsim_apply_info (c_loc of a TARGET), or c_null_ptr
+     END FUNCTION
+     !> the entries [k0, k0 + nk) of the plan of the last samsim_apply_resample, 0-based column indices
+     INTEGER(c_int) FUNCTION samsim_get_copy_plan(h, k0, nk, src, dst) BIND(C, name='samsim_get_copy_plan')
+       IMPORT
+       TYPE(c_ptr), VALUE :: h
+       INTEGER(c_int64_t), VALUE :: k0, nk
+       INTEGER(c_int64_t), INTENT(out) :: src(*), dst(*)
      END FUNCTION
      !> the HIP device ordinal of the handle and its PCI bus id (pci_bus_id: at least 16 characters) (ABI 5)
      INTEGER(c_int) FUNCTION samsim_get_device(h, device, pci_bus_id, len) BIND(C, name='samsim_get_device')

@@ -962,9 +962,9 @@ int samsim_get_weighted_profile_histogram(samsim_handle *h, const samsim_profile
  *     changes nothing; |N_c - m w_c / W| is at most 1 (SYSTEMATIC) and below 2 (STRATIFIED) up to the rounding of C.
  *   Scratch: SAMSIM_RESAMPLE_SCRATCH_BYTES of device memory whatever ncol and m are -- the ranges' sums, bases and integer partials,
  *     then the result --, allocated on first use and freed by samsim_destroy; the two rows are not counted in it.
- *   Not in scope.  Any write to the ensemble, or a device-side copy of columns; multinomial or residual resampling; a draw across
- *     the handles of several ranks (each rank resamples its own shard; a global draw needs the ranks' W, which info returns); the
- *     Fortran host's namelist.
+ *   Not in scope.  Any write to the ensemble: putting the copies where the dropped members were is samsim_apply_resample, below;
+ *     multinomial or residual resampling; a draw across the handles of several ranks (each rank resamples its own shard; a global
+ *     draw needs the ranks' W, which info returns); the Fortran host's namelist.
  *   Errors, all found before any device work, in this order.  samsim_resample: SAMSIM_ERR_ARG for h NULL; with spec NULL: info not
  *     NULL is SAMSIM_ERR_ARG, else the rows are removed (also when there are none); SAMSIM_ERR_ABI for a wrong struct_size;
  *     SAMSIM_ERR_ARG for a bad kind; no weight row; the group checks of samsim_get_covariance; m outside
@@ -988,6 +988,70 @@ typedef struct samsim_resample_info {   /* 48 bytes */
 int samsim_resample(samsim_handle *h, const samsim_resample_spec *spec, samsim_resample_info *info /* or NULL */);
 int samsim_get_offspring(samsim_handle *h, int64_t col0, int64_t ncols, double *out /*[ncols]*/);
 int samsim_get_ancestors(samsim_handle *h, int64_t k0, int64_t nk, int64_t *out /*[nk]*/);
+
+/* Applying a resample on the device: whole columns copied in place.  The step that makes the scored, weighted and resampled ensemble
+ * a particle filter: the copies of the members the data support go where the members they rule out were.  Through the host that is
+ * samsim_get_columns of the ancestors followed by samsim_set_state, both bound by a copy through pageable host memory and the first
+ * by SAMSIM_SELECT_MAX_OUT columns a call; here the data never leave the device.  The step kernel is not touched, nothing is written
+ * but what the call names, and every result is defined as the bytes of a route that already exists.  The entry points were added
+ * without a change of SAMSIM_ABI_VERSION (it stays 6): new symbols only.
+ *
+ *   samsim_copy_columns: entry k overwrites column dst[k] with column src[k], 1 <= n <= ncol.  Afterwards every getter returns for
+ *     dst[k] what it would return after this route through the host, on the same handle:
+ *       1. samsim_get_columns(src) with narr = SAMSIM_NARR, then samsim_set_state at dst[k];
+ *       2. samsim_set_status with the status, step and layer samsim_get_columns reported for the source: a copy of a stopped column
+ *          is a stopped column;
+ *       3. with tracers: samsim_get_tracer_state(src), then samsim_set_tracer_state(dst); the concentration below stays with the slot;
+ *       4. with SAMSIM_COPY_TRACKS: samsim_get_tracks, then samsim_set_track_state, for every track; with SAMSIM_COPY_SCORES:
+ *          samsim_get_scores, then samsim_set_score_state.
+ *     So of the destination: every layer of the fifteen public arrays becomes the layer value samsim_get_columns forms for the source
+ *     (S_abs with the clamp and S_bu as the quotient over the active layers of a running source once the kernel has run, the stored
+ *     element otherwise); the scalars below SAMSIM_S_DT2M, N_active, status, step and layer are the source's; the next step of the
+ *     column runs the full first sweep, exactly as after samsim_set_state (the hand-over block of the up sweep is not copied, as
+ *     samsim_set_state does not write it); the functionals are evaluated again before their next use.  Not written: the work
+ *     counters, the labels, the weight row, the offspring row, the ancestor list, the output window, and every column that is not a
+ *     destination.  Sources are only read.  Without SAMSIM_COPY_FORCING the scalars from SAMSIM_S_DT2M on, the forcing set of
+ *     samsim_set_forcing_sites and the two rows of samsim_set_ocean stay with the slot, as with samsim_set_state; with it they are
+ *     copied where they exist, so that a parameter ensemble keeps each particle's parameters.
+ *     Duplicate sources are allowed: one source feeding many destinations is the normal case.
+ *   samsim_apply_resample: the pair list from the offspring row N of the last samsim_resample, on the device, then the copy.
+ *       The POOL is the columns with status 0 now whose label passes the group of that samsim_resample call.
+ *       free   = the pool columns with N_c == 0, ascending;
+ *       copies = for each column in ascending order, N_c - 1 entries of that column's index where N_c >= 2;
+ *       entry k of the plan is (src = copies[k], dst = free[k]).
+ *     Survivors keep their slot, no source is a destination, and the copy is in place: there is no second buffer.  dst ascends
+ *     strictly and src does not descend.  The plan BALANCES when n_free == n_copies -- which needs m_drawn == n_pool: a resample
+ *     with m other than the pool size cannot be applied in place -- and no column with N_c >= 1 has left the pool since the draw.
+ *     A plan that does not balance is refused with SAMSIM_ERR_UNSUPPORTED by its counting pass, before any column is written:
+ *     nothing of the ensemble changes, the stored plan stays and info is not written.  n_copies == 0 (unit weights) returns 0 and
+ *     writes nothing of the ensemble.  A successful call marks the rows as applied: a second call without a samsim_resample in
+ *     between is refused, because after steps it would silently copy again.
+ *     info (may be NULL): n_pool the pool, n_free and n_copies the two lists' lengths (equal), n_sources the columns with N_c >= 2.
+ *   samsim_get_copy_plan: windows inside [0, n_copies) of the plan of the last successful samsim_apply_resample; it is refused
+ *     before the first.  samsim_copy_columns does not change the stored plan, and neither does a call that is refused.
+ *   Properties.  Two handles given the same calls hold the same bytes; no atomics and no hand-off between workgroups; the plan is
+ *     an ordered compaction like samsim_select_columns (count, one-wave scan, write), the totals come back in one small copy.
+ *   Device memory, allocated on first use and freed by samsim_destroy: SAMSIM_COPY_SCRATCH_BYTES for the plan's counts, two int64
+ *     rows of ncol for the lists of samsim_copy_columns and two more for the stored plan.
+ *   Not in scope.  Jitter or rejuvenation of the copies; a copy across the handles of several ranks; the plan and the applied mark
+ *     in checkpoint files; copying the hand-over block or the raw flags (the copy enters through the restart path on purpose).
+ *   Errors, all found before any device work, in this order; a call that is refused writes nothing.  samsim_copy_columns, each
+ *     SAMSIM_ERR_ARG: h, src or dst NULL; n outside 1..ncol; `what` with unknown bits; SAMSIM_COPY_TRACKS without tracks, then
+ *     SAMSIM_COPY_SCORES without sensors; an index outside [0, ncol); a dst listed twice; a column that is both a dst and a src.
+ *     samsim_apply_resample, each SAMSIM_ERR_ARG: h NULL; the checks of `what` as above; no resample rows; rows already applied; the
+ *     labels of the draw's group removed since.
+ *     samsim_get_copy_plan, each SAMSIM_ERR_ARG: h, src or dst NULL; no plan applied yet; a window outside [0, n_copies).
+ *     SAMSIM_ERR_NOMEM if a list cannot be allocated. */
+#define SAMSIM_COPY_FORCING 1   /* the perturbation slots >= SAMSIM_S_DT2M, the site index, the two ocean rows */
+#define SAMSIM_COPY_TRACKS  2   /* all SAMSIM_NTF rows of every track set                                        */
+#define SAMSIM_COPY_SCORES  4   /* all SAMSIM_NSF score rows                                                     */
+#define SAMSIM_COPY_SCRATCH_BYTES (64ull << 10)   /* the plan's partials only; a constant whatever ncol is */
+typedef struct samsim_apply_info {   /* 32 bytes */
+  int64_t n_pool, n_free, n_copies, n_sources;
+} samsim_apply_info;
+int samsim_copy_columns(samsim_handle *h, int64_t n, const int64_t *src /*[n]*/, const int64_t *dst /*[n]*/, int32_t what);
+int samsim_apply_resample(samsim_handle *h, int32_t what, samsim_apply_info *info /* or NULL */);
+int samsim_get_copy_plan(samsim_handle *h, int64_t k0, int64_t nk, int64_t *src /*[nk]*/, int64_t *dst /*[nk]*/);
 
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);

@@ -294,6 +294,21 @@ class ResampleInfo(C.Structure):
                 ("argmax_offspring", C.c_int64), ("sum_w", C.c_double)]
 
 
+# what samsim_copy_columns and samsim_apply_resample copy beside the state (SAMSIM_COPY_*)
+COPY_FORCING, COPY_TRACKS, COPY_SCORES = 1, 2, 4
+COPY_SCRATCH_BYTES = 64 << 10   # SAMSIM_COPY_SCRATCH_BYTES
+
+
+class ApplyInfo(C.Structure):
+    """struct samsim_apply_info"""
+    _fields_ = [("n_pool", C.c_int64), ("n_free", C.c_int64), ("n_copies", C.c_int64), ("n_sources", C.c_int64)]
+
+
+def copy_what(forcing=False, tracks=False, scores=False) -> int:
+    """the `what` of samsim_copy_columns and samsim_apply_resample"""
+    return (COPY_FORCING if forcing else 0) | (COPY_TRACKS if tracks else 0) | (COPY_SCORES if scores else 0)
+
+
 def offspring_slot() -> int:
     """SAMSIM_OFFSPRING_SLOT: the offspring row of resample as a slot of ensemble_stats, group_stats, histogram, covariance and
     select, while the row exists"""
@@ -658,6 +673,14 @@ class Solver:
         resample_sig = {"resample": [vp, C.POINTER(ResampleSpec), C.POINTER(ResampleInfo)], "get_offspring": [vp, i64, i64, C.c_void_p],
                         "get_ancestors": [vp, i64, i64, C.c_void_p]}
         for n, a in resample_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+
+        # and the copy of whole columns on the device
+        copy_sig = {"copy_columns": [vp, i64, C.c_void_p, C.c_void_p, C.c_int32], "apply_resample": [vp, C.c_int32, C.POINTER(ApplyInfo)],
+                    "get_copy_plan": [vp, i64, i64, C.c_void_p, C.c_void_p]}
+        for n, a in copy_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -1259,6 +1282,44 @@ class Solver:
         k0 + j: get_columns of that window of the ancestor list, ready for set_state of this or another Solver"""
         assert 0 <= nk <= SELECT_MAX_OUT
         return self.get_columns(self.ancestors(k0, nk), narr, with_status)
+
+    # -- applying a resample: whole columns copied in place on the device
+    def copy_columns_raw(self, n, src, dst, what):
+        """samsim_copy_columns with the arguments as given (no checks on this side): src and dst int64 arrays or None"""
+        self._chk(self._f("copy_columns")(self._h, int(n), None if src is None else src.ctypes.data, None if dst is None else dst.ctypes.data,
+                                          int(what)), "copy_columns")
+
+    def copy_columns(self, src, dst, forcing=False, tracks=False, scores=False):
+        """overwrite column dst[k] with column src[k] on the device (samsim_copy_columns): afterwards every getter returns for dst[k]
+        what it would after get_columns(src) -> set_state(dst) -> set_status with the source's status, with the tracer amounts, and --
+        tracks, scores -- the track and score rows; forcing: also the perturbation slots, the forcing set and the ocean rows.  A dst
+        may be listed once and may not be a src; a src may feed many.  The copies take their next step through the restart path"""
+        src, dst = np.ascontiguousarray(src, dtype=np.int64), np.ascontiguousarray(dst, dtype=np.int64)
+        assert src.ndim == 1 and src.shape == dst.shape
+        self.copy_columns_raw(src.size, src, dst, copy_what(forcing, tracks, scores))
+
+    def apply_resample_raw(self, what, info=None):
+        """samsim_apply_resample with the arguments as given: info an ApplyInfo or None"""
+        self._chk(self._f("apply_resample")(self._h, int(what), None if info is None else C.byref(info)), "apply_resample")
+        if info is not None:
+            self.n_plan = int(info.n_copies)
+
+    def apply_resample(self, forcing=False, tracks=False, scores=False):
+        """put the copies of the last resample() where the dropped members were, on the device (samsim_apply_resample): the columns
+        of the pool nobody drew take, in ascending order, the surplus copies of the columns drawn more than once; survivors keep
+        their slot.  Needs a draw with m equal to the pool size, and every drawn column still running: else SamsimError -2, and
+        nothing is written.  Returns {"n_pool", "n_free", "n_copies", "n_sources"}; copy_plan() then holds the pairs"""
+        info = ApplyInfo()
+        self.apply_resample_raw(copy_what(forcing, tracks, scores), info)
+        return {"n_pool": int(info.n_pool), "n_free": int(info.n_free), "n_copies": int(info.n_copies), "n_sources": int(info.n_sources)}
+
+    def copy_plan(self, k0: int = 0, nk: int | None = None):
+        """(src, dst), int64 [nk] each: the entries [k0, k0 + nk) of the plan of the last apply_resample (samsim_get_copy_plan);
+        nk None: up to the last entry of the last apply_resample() of this Solver"""
+        n = getattr(self, "n_plan", 0) - k0 if nk is None else nk
+        src, dst = np.zeros(max(1, n), dtype=np.int64), np.zeros(max(1, n), dtype=np.int64)
+        self._chk(self._f("get_copy_plan")(self._h, k0, n, src.ctypes.data, dst.ctypes.data), "get_copy_plan")
+        return src[:max(0, n)], dst[:max(0, n)]
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

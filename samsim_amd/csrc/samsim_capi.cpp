@@ -14,6 +14,7 @@
 #include <new>
 #include <vector>
 
+#include "samsim_copy.h"
 #include "samsim_device.h"
 #include "samsim_functionals.h"
 #include "samsim_groups.h"
@@ -97,6 +98,12 @@ struct samsim_handle {
   long long *ancestors = nullptr;    // [ancestors_cap] the ancestor of every draw, the first m_drawn entries valid
   long long ancestors_cap = 0, m_drawn = 0;
   void *d_resample = nullptr;  // samsim_resample: the ranges' sums, bases and partials, then the result (kResampleScratch bytes)
+  int32_t rs_group = -1;       // the group of the last samsim_resample: the pool of samsim_apply_resample
+  bool rs_applied = false;     // samsim_apply_resample has applied the rows of the last samsim_resample
+  long long *copy_src = nullptr, *copy_dst = nullptr;   // [ncol] each: the lists of samsim_copy_columns on the device
+  long long *plan_src = nullptr, *plan_dst = nullptr;   // [ncol] each: the plan of the last samsim_apply_resample, plan_n entries
+  long long plan_n = -1;       // -1: no plan applied yet
+  void *d_copy = nullptr;      // samsim_apply_resample: the ranges' partials and offsets, then the result (kCopyScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -268,6 +275,8 @@ constexpr size_t kWPHistScratch = DEV_WPHIST_BYTES;
 static_assert(kWPHistScratch <= SAMSIM_WPHIST_SCRATCH_BYTES && SAMSIM_WPHIST_SCRATCH_BYTES <= (64ull << 20), "weighted profile histogram scratch bound of samsim.h");
 // samsim_resample: the ranges' sums, bases and integer partials, then the result (samsim_resample.h); the two rows are the handle's own
 constexpr size_t kResampleScratch = DEV_RS_BYTES;
+constexpr size_t kCopyScratch = DEV_CP_BYTES;
+static_assert(kCopyScratch <= SAMSIM_COPY_SCRATCH_BYTES, "copy scratch bound of samsim.h");
 static_assert(kResampleScratch <= SAMSIM_RESAMPLE_SCRATCH_BYTES, "resample scratch bound of samsim.h");
 
 // fill a [rows][ncol] device block with one value per row-set
@@ -713,6 +722,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->score_rows);
   (void)hipFree(h->weight_row); (void)hipFree(h->d_weight); (void)hipFree(h->d_wprof); (void)hipFree(h->d_wphist);
   (void)hipFree(h->offspring_row); (void)hipFree(h->ancestors); (void)hipFree(h->d_resample);
+  (void)hipFree(h->copy_src); (void)hipFree(h->copy_dst); (void)hipFree(h->plan_src); (void)hipFree(h->plan_dst); (void)hipFree(h->d_copy);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -1932,6 +1942,7 @@ int samsim_resample(samsim_handle *h, const samsim_resample_spec *spec, samsim_r
     (void)hipFree(h->offspring_row); (void)hipFree(h->ancestors);
     h->offspring_row = nullptr; h->ancestors = nullptr;
     h->ancestors_cap = 0; h->m_drawn = 0;
+    h->rs_applied = false;
     return SAMSIM_OK;
   }
   if (spec->struct_size != (int32_t)sizeof(samsim_resample_spec)) return SAMSIM_ERR_ABI;
@@ -1981,6 +1992,7 @@ int samsim_resample(samsim_handle *h, const samsim_resample_spec *spec, samsim_r
   HIPCHK(hipMemcpyAsync(&res, (const char *)h->d_resample + DEV_RS_RESULT_AT, sizeof(RsResult), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->m_drawn = res.m_drawn;
+  h->rs_group = spec->group; h->rs_applied = false;   // what samsim_apply_resample takes its pool from
   if (info) *info = samsim_resample_info{res.n_pos, res.m_drawn, res.n_surv, res.max_n, res.argmax, res.sum_w};
   return SAMSIM_OK;
 }
@@ -2007,6 +2019,141 @@ int samsim_get_ancestors(samsim_handle *h, int64_t k0, int64_t nk, int64_t *out)
   HIPCHK(hipStreamSynchronize(h->stream));
   if (nk == 0) return SAMSIM_OK;
   HIPCHK(hipMemcpy(out, h->ancestors + (size_t)k0, sizeof(int64_t) * (size_t)nk, hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+}  // extern "C"
+
+// ---- whole columns copied in place (samsim_copy.hip)
+namespace {
+
+constexpr int32_t kCopyAll = SAMSIM_COPY_FORCING | SAMSIM_COPY_TRACKS | SAMSIM_COPY_SCORES;
+
+// the checks of `what` samsim_copy_columns and samsim_apply_resample share, in the order samsim.h gives
+int check_copy_what(const samsim_handle *h, int32_t what) {
+  if (what & ~kCopyAll) return SAMSIM_ERR_ARG;
+  if ((what & SAMSIM_COPY_TRACKS) && !h->tracks) return SAMSIM_ERR_ARG;
+  if ((what & SAMSIM_COPY_SCORES) && !h->score_rows) return SAMSIM_ERR_ARG;
+  return SAMSIM_OK;
+}
+
+// two int64 rows of ncol, allocated together on first use
+int copy_lists(samsim_handle *h, long long **a, long long **b) {
+  if (*a && *b) return SAMSIM_OK;
+  long long *x = nullptr, *y = nullptr;
+  if (dalloc(&x, (size_t)h->ncol) != hipSuccess || dalloc(&y, (size_t)h->ncol) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(x); (void)hipFree(y);
+    return SAMSIM_ERR_NOMEM;
+  }
+  *a = x; *b = y;
+  return SAMSIM_OK;
+}
+
+// The copy of the n pairs (src[j], dst[j]) of two device lists, enqueued on the handle's stream: what include/samsim.h says of
+// samsim_copy_columns.  Sources are only read and destinations only written, so the launches do not depend on one another.
+int copy_run(samsim_handle *h, long long n, const long long *src, const long long *dst, int32_t what) {
+  const long long nc = h->ncol;
+  const size_t N = (size_t)h->cfg.nlayer;
+  h->func_dirty = true;
+  HIPCHK(samsim_launch_copy_layers(h->lay, src, dst, h->n_active, h->status, h->flags, (int)N, nc, n, h->stepped ? 1 : 0, h->stream));
+  // the perturbation slots (>= SAMSIM_S_DT2M) belong to the forcing: they stay with the slot unless the call asks for them
+  const long long nscal = (what & SAMSIM_COPY_FORCING) ? (long long)SAMSIM_NSCAL : (long long)SAMSIM_S_DT2M;
+  HIPCHK(samsim_launch_copy_rows8(h->scal, nscal, nc, src, dst, n, h->stream));
+  HIPCHK(samsim_launch_copy_rows4(h->n_active, 1, nc, src, dst, n, h->stream));
+  HIPCHK(samsim_launch_copy_rows4(h->status, 1, nc, src, dst, n, h->stream));
+  HIPCHK(samsim_launch_copy_rows4(h->err_layer, 1, nc, src, dst, n, h->stream));
+  HIPCHK(samsim_launch_copy_rows8(h->err_step, 1, nc, src, dst, n, h->stream));
+  // the next step of the copies runs the full first sweep and treats RAY as the previous step's Rayleigh numbers, as after samsim_set_state
+  HIPCHK(samsim_launch_copy_fill4(h->flags, nc, dst, n, COLF_DIRTY | COLF_RESTART, h->stream));
+  if (h->n_bgc > 0) HIPCHK(samsim_launch_copy_rows8(h->bgc, (long long)h->n_bgc * (long long)N, nc, src, dst, n, h->stream));
+  if (what & SAMSIM_COPY_TRACKS) HIPCHK(samsim_launch_copy_rows8(h->tracks, (long long)h->ntracks * SAMSIM_NTF, nc, src, dst, n, h->stream));
+  if (what & SAMSIM_COPY_SCORES) HIPCHK(samsim_launch_copy_rows8(h->score_rows, (long long)SAMSIM_NSF, nc, src, dst, n, h->stream));
+  if (what & SAMSIM_COPY_FORCING) {
+    if (h->site) HIPCHK(samsim_launch_copy_rows4(h->site, 1, nc, src, dst, n, h->stream));
+    if (h->ocean_dflq) HIPCHK(samsim_launch_copy_rows8(h->ocean_dflq, 1, nc, src, dst, n, h->stream));
+    if (h->ocean_sbu) HIPCHK(samsim_launch_copy_rows8(h->ocean_sbu, 1, nc, src, dst, n, h->stream));
+  }
+  return SAMSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int samsim_copy_columns(samsim_handle *h, int64_t n, const int64_t *src, const int64_t *dst, int32_t what) {
+  // every check first, in the order samsim.h gives: a call that is refused writes nothing
+  if (!h || !src || !dst) return SAMSIM_ERR_ARG;
+  if (n < 1 || n > h->ncol) return SAMSIM_ERR_ARG;
+  int rc = check_copy_what(h, what);
+  if (rc) return rc;
+  for (int64_t j = 0; j < n; ++j)
+    if (src[j] < 0 || src[j] >= h->ncol || dst[j] < 0 || dst[j] >= h->ncol) return SAMSIM_ERR_ARG;
+  std::vector<unsigned char> is_dst;
+  try { is_dst.assign((size_t)h->ncol, 0); } catch (const std::bad_alloc &) { return SAMSIM_ERR_NOMEM; }
+  for (int64_t j = 0; j < n; ++j) {
+    if (is_dst[(size_t)dst[j]]) return SAMSIM_ERR_ARG;
+    is_dst[(size_t)dst[j]] = 1;
+  }
+  for (int64_t j = 0; j < n; ++j)
+    if (is_dst[(size_t)src[j]]) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  rc = copy_lists(h, &h->copy_src, &h->copy_dst);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(h->copy_src, src, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->copy_dst, dst, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  rc = copy_run(h, n, h->copy_src, h->copy_dst, what);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SAMSIM_OK;
+}
+
+int samsim_apply_resample(samsim_handle *h, int32_t what, samsim_apply_info *info) {
+  if (!h) return SAMSIM_ERR_ARG;
+  int rc = check_copy_what(h, what);
+  if (rc) return rc;
+  if (!h->offspring_row) return SAMSIM_ERR_ARG;
+  if (h->rs_applied) return SAMSIM_ERR_ARG;
+  // the labels may have been removed since the draw: the pool of a group cannot be formed without them
+  if (!good_group(h, h->rs_group)) return SAMSIM_ERR_ARG;
+  rc = use(h);
+  if (rc) return rc;
+  rc = copy_lists(h, &h->plan_src, &h->plan_dst);
+  if (rc) return rc;
+  HIPCHK(scratch(&h->d_copy, kCopyScratch));
+  const CpGrid grid = cp_grid(h->ncol);
+  CpParams p{};
+  p.offspring = h->offspring_row; p.status = h->status; p.labels = labels_for(h, h->rs_group);
+  p.ncol = h->ncol; p.per = grid.per; p.ranges = grid.ranges; p.group = h->rs_group;
+  HIPCHK(samsim_launch_copy_plan_count(&p, h->d_copy, h->stream));
+  CpResult res;
+  HIPCHK(hipMemcpyAsync(&res, (const char *)h->d_copy + DEV_CP_RESULT_AT, sizeof(CpResult), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // the counting pass decides, before any column and before the stored plan is written
+  if (!cp_balanced(res) || res.n_copies > h->ncol) return SAMSIM_ERR_UNSUPPORTED;
+  if (res.n_copies > 0) {
+    HIPCHK(samsim_launch_copy_plan_write(&p, h->d_copy, h->plan_src, h->plan_dst, h->ncol, h->stream));
+    rc = copy_run(h, res.n_copies, h->plan_src, h->plan_dst, what);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  h->plan_n = res.n_copies;
+  h->rs_applied = true;
+  if (info) *info = samsim_apply_info{res.n_pool, res.n_free, res.n_copies, res.n_sources};
+  return SAMSIM_OK;
+}
+
+int samsim_get_copy_plan(samsim_handle *h, int64_t k0, int64_t nk, int64_t *src, int64_t *dst) {
+  if (!h || !src || !dst) return SAMSIM_ERR_ARG;
+  if (h->plan_n < 0) return SAMSIM_ERR_ARG;
+  if (k0 < 0 || nk < 0 || k0 > h->plan_n || nk > h->plan_n - k0) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (nk == 0) return SAMSIM_OK;
+  HIPCHK(hipMemcpy(src, h->plan_src + (size_t)k0, sizeof(int64_t) * (size_t)nk, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(dst, h->plan_dst + (size_t)k0, sizeof(int64_t) * (size_t)nk, hipMemcpyDeviceToHost));
   return SAMSIM_OK;
 }
 
