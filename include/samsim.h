@@ -1033,7 +1033,7 @@ int samsim_get_ancestors(samsim_handle *h, int64_t k0, int64_t nk, int64_t *out 
  *     an ordered compaction like samsim_select_columns (count, one-wave scan, write), the totals come back in one small copy.
  *   Device memory, allocated on first use and freed by samsim_destroy: SAMSIM_COPY_SCRATCH_BYTES for the plan's counts, two int64
  *     rows of ncol for the lists of samsim_copy_columns and two more for the stored plan.
- *   Not in scope.  Jitter or rejuvenation of the copies; a copy across the handles of several ranks; the plan and the applied mark
+ *   Not in scope.  Jitter of the copies' state (their parameters: samsim_jitter, below); a copy across the handles of several ranks; the plan and the applied mark
  *     in checkpoint files; copying the hand-over block or the raw flags (the copy enters through the restart path on purpose).
  *   Errors, all found before any device work, in this order; a call that is refused writes nothing.  samsim_copy_columns, each
  *     SAMSIM_ERR_ARG: h, src or dst NULL; n outside 1..ncol; `what` with unknown bits; SAMSIM_COPY_TRACKS without tracks, then
@@ -1052,6 +1052,77 @@ typedef struct samsim_apply_info {   /* 32 bytes */
 int samsim_copy_columns(samsim_handle *h, int64_t n, const int64_t *src /*[n]*/, const int64_t *dst /*[n]*/, int32_t what);
 int samsim_apply_resample(samsim_handle *h, int32_t what, samsim_apply_info *info /* or NULL */);
 int samsim_get_copy_plan(samsim_handle *h, int64_t k0, int64_t nk, int64_t *src /*[nk]*/, int64_t *dst /*[nk]*/);
+
+/* Rejuvenation: the per-column parameters jittered on the device.  The model is deterministic: what tells member c from member c' is
+ * its perturbation -- the slots SAMSIM_S_DT2M and SAMSIM_S_PRECIP_SCALE and the two rows of samsim_set_ocean.  After
+ * samsim_apply_resample with SAMSIM_COPY_FORCING a member drawn five times is five identical columns that stay identical, so every
+ * resample cycle lowers the number of distinct members and nothing raises it again.  samsim_jitter is the kernel-shrinkage step of
+ * Liu and West (2001) on those rows: each value is pulled towards a centre and moved by a normal deviate that belongs to the column.
+ * Through the host that is samsim_get_state of the scalar rows, noise drawn there and samsim_set_forcing_sites with the tables again;
+ * here the rows never leave the device.  The step kernel is not touched; the new parameters take effect at the next step (the kernel
+ * reads the two slots every step and the ocean rows at the head of every launch).  New symbols only: SAMSIM_ABI_VERSION stays 6.
+ *
+ *   Rows.  SAMSIM_JT_DT2M and SAMSIM_JT_PRECIP_SCALE are the scalar rows of those names, SAMSIM_JT_DFL_Q_BOTTOM and
+ *     SAMSIM_JT_S_BU_BOTTOM the first and the second row of samsim_set_ocean; a target whose row does not exist is refused.
+ *   Which columns are written.  The POOL is the columns with status 0 now whose label passes `group` (-1: every column, no labels
+ *     needed).  SAMSIM_JITTER_POOL writes every pool column.  SAMSIM_JITTER_COPIES writes, of the destination list of the last
+ *     successful samsim_apply_resample (the stored plan), the columns whose status is 0 now; group must be -1, the plan carries the
+ *     group of its draw.  Sources and survivors keep their values: only the duplicates move.  Every other column keeps its bytes.
+ *   The normal deviate eps of (seed, column c, target t), Marsaglia's polar method on a counter-based stream: for attempt
+ *     a = 0, 1, ... < SAMSIM_JITTER_MAX_ATTEMPTS, k = (c << 8) | (t << 6) | (a << 1), x = 2 * ((mix(seed, k) >> 11) * 2^-53) - 1 and y
+ *     the same from k | 1 (both exact), s = x*x + y*y (two rounded products, the rounded sum); mix is the splitmix64 finaliser of
+ *     seed + (k + 1) * 0x9E3779B97F4A7C15, the mixer of SAMSIM_RESAMPLE_STRATIFIED.  The first attempt with 0 < s < 1 is taken and
+ *     eps = x * sqrt((-2.0 * log(s)) / s): the library's own logarithm (a fixed sequence of fused multiply-adds and one IEEE
+ *     quotient, ~1e-16 absolute), one rounded product, one IEEE division, the correctly rounded square root, one product.  Without an
+ *     accepted attempt (probability (1 - pi/4)^32 ~ 4e-22) eps = 0.  The key is the target, not the position of the term, and the
+ *     column, not the thread: the deviate of a column does not depend on `which`, `group`, ncol, the other terms or the grid.
+ *   The new value of term i for theta = row[c]: v = centre + shrink * (theta - centre) (the difference is rounded, then the product,
+ *     then the sum); v = v + sigma * eps (the product is rounded, then the sum); if v < lo then v = lo and the column counts in
+ *     n_lo[i], else if v > hi then v = hi and the column counts in n_hi[i].  A NaN compares false twice and is written as a NaN.
+ *     Nothing is fused.  For Liu and West's step with the discount delta: a = (3 delta - 1) / (2 delta), centre the mean of the row
+ *     over the pool, shrink = a, sigma = sqrt(1 - a * a) * the row's standard deviation (samsim_get_covariance gives both).
+ *   info (may be NULL): n_written the columns written, the same for every term; n_lo and n_hi per term.  Integer reductions in the
+ *     style of the copy plan: the workgroups' counts from wave ballots, a one-wave merge, one small copy; no atomics.
+ *   Not written: anything but the named rows -- not the state, status, clock, work counters, output snapshot, labels, tracks,
+ *     scores, weight row, offspring row or the stored plan; the functionals are not marked stale (none reads a parameter).
+ *   Properties.  Two handles given the same calls hold the same bytes.  The call is enqueued on the handle's first stream and
+ *     returns when the totals have arrived.
+ *   Device memory, allocated on first use and freed by samsim_destroy: SAMSIM_JITTER_SCRATCH_BYTES for the counts.
+ *   Not in scope.  Jitter of the state itself (enthalpy, salt and mass have to stay consistent); per-column physical parameters
+ *     beyond the four rows; the jittered rows in checkpoint files (samsim_get_state and samsim_get_ocean return all four).
+ *   Errors, all found before any device work, in this order; a call that is refused writes nothing.  SAMSIM_ERR_ARG for h or spec
+ *     NULL; SAMSIM_ERR_ABI for a wrong struct_size; SAMSIM_ERR_ARG for a bad `which`, then nterms outside 1..4; then per term, in
+ *     order, each SAMSIM_ERR_ARG: a bad target; a target listed twice; reserved != 0; a non-finite centre, shrink or sigma; shrink
+ *     outside [0, 1]; sigma < 0; a NaN bound or lo > hi (infinite bounds are allowed); lo < 0 for SAMSIM_JT_S_BU_BOTTOM
+ *     (samsim_set_ocean refuses a negative salinity).  Then SAMSIM_ERR_ARG for a target whose ocean row is not set; with POOL the
+ *     group checks of samsim_get_covariance; with COPIES SAMSIM_ERR_ARG for group != -1, then for no plan applied yet; a plan with
+ *     n_copies == 0 returns 0 with n_written == 0.
+ *
+ *   samsim_get_ocean: the window [col0, col0 + ncols) of the rows of samsim_set_ocean (either pointer may be NULL).
+ *     SAMSIM_ERR_ARG for h NULL, a requested row that is not set, or a window outside [0, ncol).
+ *   SAMSIM_OCEAN_SLOT(i), i = 0 the flux offset and i = 1 the salinity below, is accepted wherever a slot is while that row exists:
+ *     the posterior of an ocean parameter comes from the reductions that exist. */
+#define SAMSIM_JITTER_MAX_TERMS 4
+#define SAMSIM_JITTER_MAX_ATTEMPTS 32
+#define SAMSIM_JITTER_SCRATCH_BYTES (320ull << 10)   /* the ranges' counts only; a constant whatever ncol is */
+#define SAMSIM_OCEAN_SLOT(i) (0x60000 + (i))
+enum samsim_jitter_target { SAMSIM_JT_DT2M = 0, SAMSIM_JT_PRECIP_SCALE, SAMSIM_JT_DFL_Q_BOTTOM, SAMSIM_JT_S_BU_BOTTOM };
+enum samsim_jitter_which  { SAMSIM_JITTER_POOL = 0, SAMSIM_JITTER_COPIES = 1 };
+typedef struct samsim_jitter_term {   /* 48 bytes */
+  int32_t target, reserved;
+  double centre, shrink, sigma, lo, hi;
+} samsim_jitter_term;
+typedef struct samsim_jitter_spec {   /* 216 bytes */
+  int32_t struct_size, which, group, nterms;
+  uint64_t seed;
+  samsim_jitter_term term[SAMSIM_JITTER_MAX_TERMS];
+} samsim_jitter_spec;
+typedef struct samsim_jitter_info {   /* 72 bytes */
+  int64_t n_written, n_lo[SAMSIM_JITTER_MAX_TERMS], n_hi[SAMSIM_JITTER_MAX_TERMS];
+} samsim_jitter_info;
+int samsim_jitter(samsim_handle *h, const samsim_jitter_spec *spec, samsim_jitter_info *info /* or NULL */);
+int samsim_get_ocean(samsim_handle *h, int64_t col0, int64_t ncols, double *dfl_q_bottom /*[ncols] or NULL*/,
+                     double *S_bu_bottom /*[ncols] or NULL*/);
 
 void samsim_destroy(samsim_handle *h);
 const char *samsim_strerror(int code);

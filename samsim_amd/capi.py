@@ -315,6 +315,96 @@ def offspring_slot() -> int:
     return 0x50000
 
 
+# the rejuvenation of the resampled ensemble (samsim_jitter)
+JITTER_MAX_TERMS = 4                # SAMSIM_JITTER_MAX_TERMS
+JITTER_MAX_ATTEMPTS = 32            # SAMSIM_JITTER_MAX_ATTEMPTS
+JITTER_SCRATCH_BYTES = 320 << 10    # SAMSIM_JITTER_SCRATCH_BYTES
+# enum samsim_jitter_target: the two perturbation slots of the forcing, then the two rows of set_ocean
+JITTER_TARGETS = ["dT2m", "precip_scale", "dfl_q_bottom", "S_bu_bottom"]
+JT = {n: i for i, n in enumerate(JITTER_TARGETS)}
+# enum samsim_jitter_which
+JITTER_WHICH = {"pool": 0, "copies": 1}
+OCEAN_ROWS = ["dfl_q_bottom", "S_bu_bottom"]
+
+
+class JitterTerm(C.Structure):
+    """samsim_jitter_term: the row `target` becomes centre + shrink * (row - centre) + sigma * eps, kept within [lo, hi]"""
+    _fields_ = [("target", C.c_int32), ("reserved", C.c_int32), ("centre", C.c_double), ("shrink", C.c_double), ("sigma", C.c_double),
+                ("lo", C.c_double), ("hi", C.c_double)]
+
+    @staticmethod
+    def make(target, centre=0.0, shrink=1.0, sigma=0.0, lo=-np.inf, hi=np.inf) -> "JitterTerm":
+        """target from JITTER_TARGETS or its number"""
+        t = JT[target] if isinstance(target, str) else int(target)
+        return JitterTerm(t, 0, float(centre), float(shrink), float(sigma), float(lo), float(hi))
+
+
+class JitterSpec(C.Structure):
+    """samsim_jitter_spec: up to JITTER_MAX_TERMS terms over the pool (status 0, label `group` or -1 for any) or over the copies of the
+    last apply_resample, the deviates keyed by (seed, column, target)"""
+    _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("group", C.c_int32), ("nterms", C.c_int32), ("seed", C.c_uint64),
+                ("term", JitterTerm * JITTER_MAX_TERMS)]
+
+    @staticmethod
+    def make(terms, which="pool", seed=0, group=None) -> "JitterSpec":
+        """terms JitterTerm's (at most JITTER_MAX_TERMS are stored; nterms is their number as given); which from JITTER_WHICH or its
+        number"""
+        terms = list(terms)
+        w = JITTER_WHICH[which] if isinstance(which, str) else int(which)
+        spec = JitterSpec(C.sizeof(JitterSpec), w, -1 if group is None else int(group), len(terms), int(seed) & (2 ** 64 - 1))
+        for i, t in enumerate(terms[:JITTER_MAX_TERMS]):
+            spec.term[i] = t
+        return spec
+
+
+class JitterInfo(C.Structure):
+    """samsim_jitter_info"""
+    _fields_ = [("n_written", C.c_int64), ("n_lo", C.c_int64 * JITTER_MAX_TERMS), ("n_hi", C.c_int64 * JITTER_MAX_TERMS)]
+
+    def as_dict(self, nterms=JITTER_MAX_TERMS):
+        return {"n_written": int(self.n_written), "n_lo": [int(x) for x in self.n_lo[:nterms]], "n_hi": [int(x) for x in self.n_hi[:nterms]]}
+
+
+def ocean_slot(name) -> int:
+    """SAMSIM_OCEAN_SLOT(i): a row of set_ocean ("dfl_q_bottom" or "S_bu_bottom", or its number) as a slot of ensemble_stats,
+    group_stats, histogram, covariance, select and the weighted reductions, while that row exists"""
+    return 0x60000 + (OCEAN_ROWS.index(name) if isinstance(name, str) else int(name))
+
+
+def jitter_slot(target) -> int:
+    """the slot that reads the row of a jitter target: the scalar of that name, or ocean_slot"""
+    t = JITTER_TARGETS[target] if isinstance(target, (int, np.integer)) else target
+    return ocean_slot(t) if t in OCEAN_ROWS else S[t]
+
+
+def liu_west(delta):
+    """(a, h) of Liu and West's kernel shrinkage for the discount factor delta in (0, 1]: a = (3 delta - 1) / (2 delta) the shrinkage
+    of each value towards the mean, h = sqrt(1 - a^2) the width of the kernel in standard deviations; mean and variance of the
+    ensemble are kept"""
+    delta = float(delta)
+    if not 1.0 / 3.0 <= delta <= 1.0:
+        raise ValueError("delta outside [1/3, 1]")
+    a = (3.0 * delta - 1.0) / (2.0 * delta)
+    return a, float(np.sqrt(1.0 - a * a))
+
+
+_M64 = (1 << 64) - 1
+
+
+def mix64(seed, k) -> int:
+    """rs_mix of samsim_resample.h: the splitmix64 finaliser of seed + (k + 1) * 0x9E3779B97F4A7C15 in wrapping 64-bit arithmetic, the
+    mixer of the stratified draw and of the jitter's deviates"""
+    z = (int(seed) + (int(k) + 1) * 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def rs_offset(seed, k) -> float:
+    """rs_offset of samsim_resample.h: the upper 53 bits of mix64(seed, k) as a double in [0, 1)"""
+    return float(mix64(seed, k) >> 11) * 2.0 ** -53
+
+
 def weighted_quantile_bracket(wsum, v0, dv, q):
     """(lo, hi) with the weighted q-quantile of the data in [lo, hi), from the sums of Solver.weighted_histogram (nvbins + 2
     entries): the quantile is the smallest value whose cumulative weight reaches q times the total; i = the first entry of positive
@@ -681,6 +771,12 @@ class Solver:
         copy_sig = {"copy_columns": [vp, i64, C.c_void_p, C.c_void_p, C.c_int32], "apply_resample": [vp, C.c_int32, C.POINTER(ApplyInfo)],
                     "get_copy_plan": [vp, i64, i64, C.c_void_p, C.c_void_p]}
         for n, a in copy_sig.items():
+            if hasattr(self._lib, self._p + n):
+                f = self._f(n)
+                f.argtypes, f.restype = a, C.c_int
+        # and the jitter of the per-column parameters, with the getter of the ocean rows
+        jitter_sig = {"jitter": [vp, C.POINTER(JitterSpec), C.POINTER(JitterInfo)], "get_ocean": [vp, i64, i64, C.c_void_p, C.c_void_p]}
+        for n, a in jitter_sig.items():
             if hasattr(self._lib, self._p + n):
                 f = self._f(n)
                 f.argtypes, f.restype = a, C.c_int
@@ -1320,6 +1416,66 @@ class Solver:
         src, dst = np.zeros(max(1, n), dtype=np.int64), np.zeros(max(1, n), dtype=np.int64)
         self._chk(self._f("get_copy_plan")(self._h, k0, n, src.ctypes.data, dst.ctypes.data), "get_copy_plan")
         return src[:max(0, n)], dst[:max(0, n)]
+
+    # -- rejuvenation: the per-column parameters jittered on the device, and one assimilation cycle from end to end
+    def get_ocean(self, col0: int = 0, ncols: int | None = None, dfl_q_bottom=True, S_bu_bottom=True):
+        """(dfl_q_bottom, S_bu_bottom), float64 [ncols] each or None where not asked for: the window of the rows of set_ocean
+        (samsim_get_ocean); a row that is asked for and not set is SamsimError -1"""
+        n = self.ncol - col0 if ncols is None else ncols
+        d = np.zeros(max(0, n)) if dfl_q_bottom else None
+        s = np.zeros(max(0, n)) if S_bu_bottom else None
+        self._chk(self._f("get_ocean")(self._h, col0, n, None if d is None else d.ctypes.data, None if s is None else s.ctypes.data),
+                  "get_ocean")
+        return d, s
+
+    def jitter_raw(self, spec, info=None):
+        """samsim_jitter with the arguments as given (no checks on this side): spec a JitterSpec or None, info a JitterInfo or None"""
+        self._chk(self._f("jitter")(self._h, None if spec is None else C.byref(spec), None if info is None else C.byref(info)), "jitter")
+
+    def jitter(self, terms, which="pool", seed=0, group=None):
+        """shrink and jitter the parameter rows the terms (JitterTerm.make) name, on the device (samsim_jitter): row = centre +
+        shrink * (row - centre) + sigma * eps within [lo, hi], eps the normal deviate of (seed, column, target).  which="pool": the
+        running columns -- with group: of that label --; "copies": the destinations of the last apply_resample that still run.
+        Returns {"n_written", "n_lo" [nterms], "n_hi" [nterms]}"""
+        terms = list(terms)
+        info = JitterInfo()
+        self.jitter_raw(JitterSpec.make(terms, which, seed, group), info)
+        return info.as_dict(len(terms))
+
+    def rejuvenate(self, targets, delta=0.98, seed=0, which="pool", group=None, bounds=None):
+        """Liu and West's kernel shrinkage of the parameter rows `targets` (names from JITTER_TARGETS): mean and variance of each
+        row over the pool (one covariance call on their slots), then one jitter with centre = mean, shrink = a and sigma = h *
+        sqrt(var), (a, h) = liu_west(delta), so the pool keeps its mean and variance while equal members part.  bounds: {target:
+        (lo, hi)}.  Returns the jitter's info with the moments used: "count", "mean" and "var" [ntargets], "a" and "h" """
+        targets = [JITTER_TARGETS[t] if isinstance(t, (int, np.integer)) else t for t in targets]
+        a, h = liu_west(delta)
+        count, mean, cov = self.covariance_raw([jitter_slot(t) for t in targets], -1 if group is None else int(group))
+        var = np.diag(cov)[:len(targets)].copy()
+        bounds = bounds or {}
+        free = {t: ((0.0 if t == "S_bu_bottom" else -np.inf), np.inf) for t in targets}     # a salinity below is never negative
+        terms = [JitterTerm.make(t, mean[i], a, h * float(np.sqrt(max(var[i], 0.0))), *bounds.get(t, free[t]))
+                 for i, t in enumerate(targets)]
+        info = self.jitter(terms, which, seed, group)
+        info.update(count=count, mean=mean[:len(targets)].copy(), var=var, a=a, h=h)
+        return info
+
+    def assimilate(self, obs, weight=None, scale=1.0, ess_frac=0.5, seed=0, targets=("dT2m",), delta=0.98, tracks=False):
+        """one assimilation cycle of the whole handle: score the sensors against `obs`, weight the members by the accumulated misfit
+        (Gauss, `scale`), and when the effective sample size falls below ess_frac * n_in: a systematic resample of n_in draws, the
+        copies put in place with their forcing (and tracks), the targets rejuvenated (rejuvenate with delta) and the scores reset.
+        Offset and jitter seed follow from `seed` and the clock's step, so two handles given the same calls hold the same bytes.
+        Returns {"ess", "n_in", "resampled", "n_copies", "n_survivors", "jitter"}"""
+        self.score(obs, weight)
+        w = self.set_weights(score_slot("J_SUM"), "gauss", scale)
+        out = {"ess": w["ess"], "n_in": w["n_in"], "resampled": False, "n_copies": 0, "n_survivors": w["n_in"], "jitter": None}
+        if w["ess"] < ess_frac * w["n_in"]:
+            step = int(self.get_clock().step)
+            r = self.resample(w["n_in"], "systematic", u0=rs_offset(seed, 2 * step))
+            p = self.apply_resample(forcing=True, tracks=tracks)
+            out["jitter"] = self.rejuvenate(list(targets), delta, mix64(seed, 2 * step + 1))
+            self.reset_scores()
+            out.update(resampled=True, n_copies=p["n_copies"], n_survivors=r["n_survivors"])
+        return out
 
     def run_to_output(self) -> Output:
         """advance to (and through) the next output point of mo_grotz.f90:340 and return its snapshot"""

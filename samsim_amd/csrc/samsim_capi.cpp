@@ -19,6 +19,7 @@
 #include "samsim_functionals.h"
 #include "samsim_groups.h"
 #include "samsim_hist.h"
+#include "samsim_jitter.h"
 #include "samsim_pass_plan.h"
 #include "samsim_resample.h"
 #include "samsim_select.h"
@@ -104,6 +105,7 @@ struct samsim_handle {
   long long *plan_src = nullptr, *plan_dst = nullptr;   // [ncol] each: the plan of the last samsim_apply_resample, plan_n entries
   long long plan_n = -1;       // -1: no plan applied yet
   void *d_copy = nullptr;      // samsim_apply_resample: the ranges' partials and offsets, then the result (kCopyScratch bytes)
+  void *d_jitter = nullptr;    // samsim_jitter: the ranges' counts, then the totals (kJitterScratch bytes)
   double *stage = nullptr;     // staging buffer of samsim_set_state / samsim_get_state (boundary layout), grown on demand up to
   size_t stage_n = 0;          // kStageBytes and kept: no hipMalloc / hipFree -- both wait for the whole device -- per call
   // passive tracers (bgc_flag 2)
@@ -277,6 +279,9 @@ static_assert(kWPHistScratch <= SAMSIM_WPHIST_SCRATCH_BYTES && SAMSIM_WPHIST_SCR
 constexpr size_t kResampleScratch = DEV_RS_BYTES;
 constexpr size_t kCopyScratch = DEV_CP_BYTES;
 static_assert(kCopyScratch <= SAMSIM_COPY_SCRATCH_BYTES, "copy scratch bound of samsim.h");
+constexpr size_t kJitterScratch = DEV_JT_BYTES;
+static_assert(kJitterScratch <= SAMSIM_JITTER_SCRATCH_BYTES, "jitter scratch bound of samsim.h");
+static_assert(sizeof(samsim_jitter_term) == 48 && sizeof(samsim_jitter_spec) == 216 && sizeof(samsim_jitter_info) == 72, "the jitter structs of samsim.h");
 static_assert(kResampleScratch <= SAMSIM_RESAMPLE_SCRATCH_BYTES, "resample scratch bound of samsim.h");
 
 // fill a [rows][ncol] device block with one value per row-set
@@ -462,7 +467,7 @@ int launch(samsim_handle *h, long long nsteps) {
 
 // a slot of the statistics: an enum samsim_scalar, SAMSIM_STAT_N_ACTIVE, SAMSIM_TRACK_SLOT(track, field) of the tracks in force, or
 // SAMSIM_FUNC_SLOT(i) of the functionals in force, or SAMSIM_SCORE_SLOT(field) while sensors are set, or SAMSIM_WEIGHT_SLOT while the
-// weight row exists, or SAMSIM_OFFSPRING_SLOT while the offspring row does
+// weight row exists, or SAMSIM_OFFSPRING_SLOT while the offspring row does, or SAMSIM_OCEAN_SLOT(i) while that row of samsim_set_ocean does
 bool func_slot(int32_t slot) { return slot >= SAMSIM_FUNC_SLOT(0) && slot < SAMSIM_FUNC_SLOT(SAMSIM_MAX_FUNCTIONALS); }
 bool score_slot(int32_t slot) { return slot >= SAMSIM_SCORE_SLOT(0) && slot < SAMSIM_SCORE_SLOT(SAMSIM_NSF); }
 bool good_slot(const samsim_handle *h, int32_t slot) {
@@ -471,6 +476,8 @@ bool good_slot(const samsim_handle *h, int32_t slot) {
   if (score_slot(slot)) return h->score_rows != nullptr;
   if (slot == SAMSIM_WEIGHT_SLOT) return h->weight_row != nullptr;
   if (slot == SAMSIM_OFFSPRING_SLOT) return h->offspring_row != nullptr;
+  if (slot == SAMSIM_OCEAN_SLOT(0)) return h->ocean_dflq != nullptr;
+  if (slot == SAMSIM_OCEAN_SLOT(1)) return h->ocean_sbu != nullptr;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks && o >= 0 && o / 32 < h->ntracks && o % 32 < SAMSIM_NTF;
 }
@@ -482,6 +489,8 @@ const double *slot_row(const samsim_handle *h, int32_t slot) {
   if (score_slot(slot)) return h->score_rows + (size_t)(slot - SAMSIM_SCORE_SLOT(0)) * (size_t)h->ncol;
   if (slot == SAMSIM_WEIGHT_SLOT) return h->weight_row;
   if (slot == SAMSIM_OFFSPRING_SLOT) return h->offspring_row;
+  if (slot == SAMSIM_OCEAN_SLOT(0)) return h->ocean_dflq;
+  if (slot == SAMSIM_OCEAN_SLOT(1)) return h->ocean_sbu;
   const int32_t o = slot - SAMSIM_TRACK_SLOT(0, 0);
   return h->tracks + ((size_t)(o / 32) * SAMSIM_NTF + (size_t)(o % 32)) * (size_t)h->ncol;
 }
@@ -723,6 +732,7 @@ void samsim_destroy(samsim_handle *h) {
   (void)hipFree(h->weight_row); (void)hipFree(h->d_weight); (void)hipFree(h->d_wprof); (void)hipFree(h->d_wphist);
   (void)hipFree(h->offspring_row); (void)hipFree(h->ancestors); (void)hipFree(h->d_resample);
   (void)hipFree(h->copy_src); (void)hipFree(h->copy_dst); (void)hipFree(h->plan_src); (void)hipFree(h->plan_dst); (void)hipFree(h->d_copy);
+  (void)hipFree(h->d_jitter);
   (void)hipFree(h->d_select);
   (void)hipFree(h->bgc); (void)hipFree(h->bgc_bot); (void)hipFree(h->bfl); (void)hipFree(h->out_bgc); (void)hipFree(h->out_bgc_bot);
   (void)hipFree(h->f_sw); (void)hipFree(h->f_lw); (void)hipFree(h->f_T2m); (void)hipFree(h->f_precip); (void)hipFree(h->site);
@@ -2154,6 +2164,59 @@ int samsim_get_copy_plan(samsim_handle *h, int64_t k0, int64_t nk, int64_t *src,
   if (nk == 0) return SAMSIM_OK;
   HIPCHK(hipMemcpy(src, h->plan_src + (size_t)k0, sizeof(int64_t) * (size_t)nk, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(dst, h->plan_dst + (size_t)k0, sizeof(int64_t) * (size_t)nk, hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+// ---- the per-column parameters: read back, and jittered on the device (samsim_jitter.hip)
+int samsim_get_ocean(samsim_handle *h, int64_t col0, int64_t ncols, double *dfl_q_bottom, double *S_bu_bottom) {
+  if (!h) return SAMSIM_ERR_ARG;
+  if ((dfl_q_bottom && !h->ocean_dflq) || (S_bu_bottom && !h->ocean_sbu)) return SAMSIM_ERR_ARG;
+  if (col0 < 0 || ncols < 0 || col0 > h->ncol || ncols > h->ncol - col0) return SAMSIM_ERR_ARG;
+  int rc = use(h);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ncols == 0) return SAMSIM_OK;
+  if (dfl_q_bottom) HIPCHK(hipMemcpy(dfl_q_bottom, h->ocean_dflq + (size_t)col0, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost));
+  if (S_bu_bottom) HIPCHK(hipMemcpy(S_bu_bottom, h->ocean_sbu + (size_t)col0, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost));
+  return SAMSIM_OK;
+}
+
+int samsim_jitter(samsim_handle *h, const samsim_jitter_spec *spec, samsim_jitter_info *info) {
+  // every check first, in the order samsim.h gives (jt_check, samsim_jitter.h): a call that is refused writes nothing
+  if (!h || !spec) return SAMSIM_ERR_ARG;
+  int rc = jt_check(spec, h->ocean_dflq != nullptr, h->ocean_sbu != nullptr, good_group(h, spec->group), h->plan_n);
+  if (rc) return rc;
+  const bool copies = spec->which == SAMSIM_JITTER_COPIES;
+  if (copies && h->plan_n == 0) {
+    if (info) *info = samsim_jitter_info{};
+    return SAMSIM_OK;
+  }
+  rc = use(h);
+  if (rc) return rc;
+  HIPCHK(scratch(&h->d_jitter, kJitterScratch));
+  JtParams p{};
+  for (int i = 0; i < spec->nterms; ++i) {
+    p.term[i] = spec->term[i];
+    switch (spec->term[i].target) {
+      case SAMSIM_JT_DT2M: p.row[i] = h->scal + (size_t)SAMSIM_S_DT2M * (size_t)h->ncol; break;
+      case SAMSIM_JT_PRECIP_SCALE: p.row[i] = h->scal + (size_t)SAMSIM_S_PRECIP_SCALE * (size_t)h->ncol; break;
+      case SAMSIM_JT_DFL_Q_BOTTOM: p.row[i] = h->ocean_dflq; break;
+      default: p.row[i] = h->ocean_sbu; break;
+    }
+  }
+  p.status = h->status;
+  p.labels = copies ? nullptr : labels_for(h, spec->group);
+  p.dst = copies ? h->plan_dst : nullptr;
+  p.ncol = h->ncol;
+  p.n = copies ? h->plan_n : h->ncol;
+  const JtGrid grid = jt_grid(p.n);
+  p.per = grid.per; p.ranges = grid.ranges;
+  p.seed = spec->seed; p.group = spec->group; p.nterms = spec->nterms;
+  HIPCHK(samsim_launch_jitter(&p, h->d_jitter, h->stream));
+  JtCounts res;
+  HIPCHK(hipMemcpyAsync(&res, (const char *)h->d_jitter + DEV_JT_RESULT_AT, sizeof(JtCounts), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (info) std::memcpy(info, &res, sizeof(JtCounts));
   return SAMSIM_OK;
 }
 
