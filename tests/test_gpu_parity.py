@@ -513,8 +513,10 @@ def test_per_column_ocean_grid_of_columns():
     # within a few per cent of thick_min, already shows 2e-3 (profiles/r3_freeze_up_windows_days64_68.json; the HIP path: 3e-4),
     # the 1 500-step windows of days 64, 65, 66 and 68 stay below 1e-13, and so does every ONE-DAY window from day 68 on
     # (profiles/r3_freeze_up_windows_1day.json: 3e-13).  So: 1 500-step windows at days 64, 65, 66 at the parity bar, the one at
-    # day 67 held to the size of that event, and from day 68 one-day windows every second day at 1e-9, like the main path's
-    # windows from the reference's records.
+    # day 67 held to the size of that event (4e-3: twice the 2e-3 of the two CPU builds, thirteen times the HIP path's 3e-4), and
+    # from day 68 one-day windows every second day at 1e-9, like the main path's windows from the reference's records.  The parity
+    # bar THROUGH day 67 -- every step of it, in 864 ten-step windows in which nothing is amplified -- is held by
+    # tests/test_gpu_event_windows.py::test_ocean_grid_day_67_first_snow_through_thick_min.
     n = 8641 * 64
     g.step(n)
     o.step(n)
@@ -531,7 +533,7 @@ def test_per_column_ocean_grid_of_columns():
         g.set_clock(time=k.time, step=k.step, n_time_out=k.n_time_out, time_counter=k.time_counter, n_outputs=k.n_outputs)
         g.step(window)
         o.step(window)
-        sg, so = check(g, o, f"ocean grid, {window} steps from day {day}", rtol=5e-3 if day == 67 else 1e-6)
+        sg, so = check(g, o, f"ocean grid, {window} steps from day {day}", rtol=4e-3 if day == 67 else 1e-6)
         spread.update(int(v) for v in so.n_active)
         if day >= 68:
             kk = np.arange(sg.nlayer)[:, None] < so.n_active[None, :]

@@ -58,7 +58,9 @@ def test_sheba_windows_started_from_the_reference_records():
         # Day 347 is the day a threshold event flips in the reference itself: its own -O2 build and its FMA build part ways there
         # by more than 1e-6 within one output interval (measured).  Round-off level differences (observed
         # elsewhere: <= 1e-11) decide which side of the threshold a step lands on, so that one window is held to the size of
-        # the event, every other window to the parity bar.
+        # the event, every other window to the parity bar.  The same 8 641 steps at the parity bar, in ten-step windows restarted from
+        # the checker: tests/test_gpu_event_windows.py::test_reference_day_347_record_to_its_day_348_record_in_ten_step_windows (and
+        # the 16 perturbed columns through days 346 to 349 beside it).
         tol = 2e-2 if day == 347 else RTOL
         for n in ["T", "psi_s", "psi_l", "S_bu", "thick", "H_abs", "S_abs", "m"]:
             floor = 1e-3 if n == "H_abs" else 1e-7

@@ -139,7 +139,12 @@ def test_tc7_simple_parametrisations_free_run_and_reference_windows():
 @pytest.mark.parametrize("tc,nout", [(2, 120), (9, 72), (6, 60), (33, 70), (34, 1417)])
 def test_tank_experiments(tc, nout):
     """testcases 2, 6, 9, 33, 34 (boundflux_flag 3, tank_flag 2, T2m schedules): the HIP path's output snapshots against the
-    reference's own records and, at the end, the full state against the oracle; the water below the ice gets saltier"""
+    reference's own records and, at the end, the full state against the oracle; the water below the ice gets saltier.
+    At the parity bar: these runs amplify nothing (the checker and its FMA build stay within 3.3e-13 of each other over the whole
+    free runs), and the HIP path stays within 3.1e-12 of the checker and 1.2e-13 of these records at every output of every run
+    (profiles/r25_event_windows.json, "tank"; the 2e-6 asserted here until then was never needed).  Testcase 6 stays at its first
+    60 of 156 outputs: the whole run is 280 800 steps of a single wave, 22 s on its own; all 156 were compared once, in that profile.
+    tests/test_gpu_event_windows.py::test_tank_budget_in_ten_step_windows tiles the worst interval of three of the runs."""
     ncol = 8
     cfg, st = getattr(tcs, f"testcase{tc}")(ncol)
     g, o = _pair(cfg, ncol, st)
@@ -150,13 +155,13 @@ def test_tank_experiments(tc, nout):
         out = g.run_to_output()
         assert out.step == ref["all_step"][i] and out.n_active[0] == ref["all_N_active"][i], f"tc{tc} output {i}"
         for n, floor in (("S_bu_bottom", 1e-7), ("thickness", 1e-6), ("bulk_salin", 1e-5), ("T_top", 1e-2), ("freeboard", 1e-6)):
-            assert rel_err(out.sc(n)[0], ref["all_s_" + n][i], floor) <= 2e-6, f"tc{tc} output {i}: {n} vs reference"
+            assert rel_err(out.sc(n)[0], ref["all_s_" + n][i], floor) <= RTOL, f"tc{tc} output {i}: {n} vs reference"
         if i in rows:
             na = int(out.n_active[0])
             for n in ["T", "psi_s", "psi_l", "S_bu", "thick"]:
-                assert rel_err(out.arr(n)[:na, 0], ref["a_" + n][rows[i], :na], 1e-6) <= 2e-6, f"tc{tc} output {i}: {n}"
+                assert rel_err(out.arr(n)[:na, 0], ref["a_" + n][rows[i], :na], 1e-6) <= RTOL, f"tc{tc} output {i}: {n}"
     o.step(g.get_clock().step)
-    sg, so = _check(g, o, f"tc{tc} end of run", rtol=2e-6)
+    sg, so = _check(g, o, f"tc{tc} end of run")
     assert so.sc("S_bu_bottom")[0] > cfg.S_bu_bottom and (sg.lay == sg.lay[:, :, :1]).all()
 
 
@@ -240,7 +245,10 @@ def test_the_five_later_era_sites_free_run_against_the_reference_records():
     80N90E meets a freeze-up event that amplifies round-off on output day 61 (ice of 8-9 layers melting back to 6): the checker
     and its own -ffp-contract=fast build part by 4e-4 there, the other four sites stay below 2e-12 for all 150 days
     (profiles/r3_site_sensitivity.json, CPU only).  So 80N90E is held to the parity bar up to day 60 and to the size of that event
-    afterwards; the other sites to the parity bar throughout."""
+    afterwards (1e-3: a small factor over the 4e-4 to 6e-4 of that record), the other sites to the parity bar throughout.  The parity
+    bar THROUGH the event (days 59 to 63 in windows of 100 steps, N_active and every layer array) and after it (one-day windows from
+    the checker's state at days 70, 100 and 130) is held by tests/test_gpu_event_windows.py, which is where a thin-snow-coupling or
+    regrid regression below the event's size would show."""
     from tests import background_runs
     more = background_runs.SITES
     run = background_runs.get("sites_free_run")       # started with the session's first GPU test: it has been running beside the others
@@ -251,11 +259,12 @@ def test_the_five_later_era_sites_free_run_against_the_reference_records():
     scalars = (("thickness", 1e-7), ("bulk_salin", 1e-7), ("freeboard", 1e-7), ("m_snow", 1e-5), ("thick_snow", 1e-7), ("T_snow", 1e-2),
                ("T_top", 1e-2), ("T2m", 1e-2), ("energy_stored", 1e-3), ("total_resist", 1e-7), ("grav_salt", 1e-9))
     worst = {s: 0.0 for s in more}
+    worst_event = 0.0
     layer_days = 0
     for i, out in enumerate(outputs):
         for c, s in enumerate(more):
             event = s == "80N90E" and i >= 60
-            tol = 5e-3 if event else RTOL
+            tol = 1e-3 if event else RTOL
             assert out.step == z[f"{s}_all_step"][i]
             if not event:
                 assert out.n_active[c] == z[f"{s}_all_N_active"][i], f"{s} output {i}: N_active {out.n_active[c]} vs {z[f'{s}_all_N_active'][i]}"
@@ -263,6 +272,8 @@ def test_the_five_later_era_sites_free_run_against_the_reference_records():
                 e = rel_err(out.sc(n)[c], z[f"{s}_all_s_{n}"][i], floor)
                 if not event:
                     worst[s] = max(worst[s], e)
+                else:
+                    worst_event = max(worst_event, e)
                 assert e <= tol, f"{s} output day {i}: {n} = {out.sc(n)[c]!r} vs the reference's {z[f'{s}_all_s_{n}'][i]!r} ({e:.2e})"
             if i in rows[s] and not event:
                 j, na = rows[s][i], int(out.n_active[c])
@@ -274,7 +285,8 @@ def test_the_five_later_era_sites_free_run_against_the_reference_records():
                     assert e <= RTOL, f"{s} output day {i}: layers of {n} rel err {e:.2e} vs the reference record"
     assert not run.status.any()
     assert layer_days >= 12 and out.n_active.max() >= 90
-    print("five sites, free run of 150 output days: worst relative deviation from the reference's records", {k: f"{v:.1e}" for k, v in worst.items()})
+    print("five sites, free run of 150 output days: worst relative deviation from the reference's records", {k: f"{v:.1e}" for k, v in worst.items()},
+          f"; 80N90E from output day 60 on: {worst_event:.1e}")
     assert max(worst.values()) <= 1e-8
 
 
